@@ -12,12 +12,20 @@ HBM.  Workload = BASELINE config 2: 384x1280, bf16, batch 4 per GPU.  Image pair
 with no data-path collective (replicas, weak scaling); value = pairs all ranks processed / max-over-
 ranks time of exactly K steps bracketed by barrier + synchronize.
 
-The JSON line also carries
-  roofline     — the dominant hand-written kernel (81-neighbour cost volume at the 1/4-res level of
-                 this workload): algorithmic bytes s*B*H*W*(2C+81) / average kernel duration measured
-                 with HIP events recorded around each launch on its stream, vs the 8 TB/s HBM peak;
-  cpu_baseline — the reference's pure-PyTorch fallback path (utils/pytorch_correlation.py algorithm,
-                 restated in oracle/) timed on this box's host cores, rank 0 at N=1 only.
+A plain run sets up, warms up, times the K steps (one window) and prints the line.
+  --dump-outputs DIR  after the timed steps, the arrays the last timed step returned (rank 0), as
+                      DIR/<name>.npy in float32 (a fixed, seeded sample when they exceed 64 MB);
+                      the inputs are the same from run to run for the same arguments
+  --full              everything else the line used to carry: --windows 3 by default (value = the
+                      median window), the one-step-in-flight latency, the literal split, the EPE
+                      against the committed reference fixture, the batch-1 evaluation path, and
+    roofline     — the dominant hand-written kernel (81-neighbour cost volume at the 1/4-res level of
+                   this workload): algorithmic bytes s*B*H*W*(2C+81) / average kernel duration measured
+                   with HIP events recorded around each launch on its stream, vs the 8 TB/s HBM peak;
+    roofline_conv, roofline_step — the largest convolution launch and the whole step vs the MFMA peak;
+    cpu_baseline — the reference's pure-PyTorch fallback path (utils/pytorch_correlation.py algorithm,
+                   restated in oracle/) timed on the host cores, rank 0 at N=1 only;
+    train_step   — the config-3 training step at N=1.
 """
 import argparse
 import json
@@ -268,6 +276,25 @@ def _median(v):
     return v[len(v) // 2]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outs, path):
+    """--dump-outputs: every tensor of `outs` (name -> tensor) as path/<name>.npy in float32.  When the whole exceeds 64 MB,
+    each array keeps the same share of its elements: a seeded sample of flat indices (sorted; the same for the same shape),
+    so that two builds of the project are compared element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in sorted(outs.items()) if torch.is_tensor(v)}
+    total = sum(a.size * 4 for a in arrs.values())
+    keep = min(1.0, (DUMP_BUDGET_BYTES - 4096 * len(arrs)) / max(total, 1))
+    for k, a in arrs.items():
+        if keep < 1.0:
+            rng = np.random.default_rng(0)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=max(1, int(a.size * keep)), replace=False))]
+        np.save(os.path.join(path, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def cpu_baseline():
     """The reference's CPU fallback (pure-PyTorch unfold correlation inside the full fp32 forward), as restated in
     oracle/ (kind "port"), on this box's host cores — BASELINE.md §3: full UPFlow_net forward at 384x1280 B=1 (the
@@ -364,6 +391,8 @@ def train_main(args, rank, world, device):
     own = time.perf_counter() - t0                   # (under DDP every step ends in a collective: the ranks' own times differ by their last step only)
     barrier()
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, device)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(dict(zip(tr._names, stats.cpu())), args.dump_outputs)       # (the loss terms the last step returned)
     stats = {k: float(v) for k, v in zip(tr._names, stats.cpu())}
     spread = rank_spread(own, args.steps, device)
     # the ONE exchange step of the path, timed on its own (outside the timed region): an all-reduce of a gradient-sized
@@ -629,7 +658,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--windows', type=int, default=3, help='timed windows of --steps steps each; value = the median window')
+    ap.add_argument('--windows', type=int, default=None,
+                    help='timed windows of --steps steps each; value = the median window (default 1; 3 under --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline: the roofline probes, the one-step-in-flight latency, '
+                         'the literal split, the EPE against the reference fixture, the evaluation path, the CPU baseline, the training step')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float32, rank 0)')
     ap.add_argument('--ramp-seconds', type=float, default=0.5, help='untimed replay before the warm-up steps (clock ramp)')
     ap.add_argument('--workload', default='config2', choices=sorted(WORKLOADS))
     ap.add_argument('--dtype', default=None, choices=sorted(DT))
@@ -656,6 +691,8 @@ def main():
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'],
                     help='process-group backend (default nccl = RCCL; gloo only for --mode launch-check on a CPU box)')
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args.gpus)                   # no external launcher: spawn one rank per GPU ourselves
@@ -717,11 +754,14 @@ def main():
         torch.cuda.synchronize(device)
 
     # clock ramp: the part idles at a low clock; a W of 10 steps is 35 ms of work, shorter than the governor's ramp, so
-    # the same (untimed, un-counted) step is replayed for --ramp-seconds before the W warm-up steps the contract asks for
-    t_ramp = time.perf_counter()
-    while time.perf_counter() - t_ramp < args.ramp_seconds:
+    # the same (untimed, un-counted) step is replayed for --ramp-seconds before the W warm-up steps the contract asks for.
+    # It ends on a whole round of the slots, so that the slot (and batch) of the last timed step depends on W and K alone.
+    n_slots = args.streams if (not args.no_graph and args.streams > 1) else 1
+    t_ramp, n_ramp = time.perf_counter(), 0
+    while time.perf_counter() - t_ramp < args.ramp_seconds or n_ramp % n_slots:
         step()
         torch.cuda.synchronize(device)
+        n_ramp += 1
     for _ in range(args.warmup):
         step()
     # `--windows` timed windows of EXACTLY K steps each, every one bracketed by barrier + synchronize on both sides and reduced with MAX
@@ -740,11 +780,14 @@ def main():
     elapsed, own = windows[len(windows) // 2]
     spread = rank_spread(own, args.steps, device)
     assert torch.isfinite(out['flow_f_out']).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)                     # (before anything below replays a slot again)
     pipelined = (not args.no_graph) and args.streams > 1
     single = None
     if pipelined:
         for r_ in pipe.runners:                                  # every slot's outputs, not only the last step's
             assert torch.isfinite(r_.out['flow_f_out']).all() and torch.isfinite(r_.out['flow_b_out']).all()
+    if pipelined and args.full:
         # the same K steps with ONE step in flight (the latency-bound schedule every earlier round reported), for continuity
         r0 = pipe.runners[0]
         for _ in range(args.warmup):
@@ -776,12 +819,14 @@ def main():
                        'pyramid_convs': 'PyTorch-ROCm' if args.torch_pyramid or (dtype == torch.float32 and args.fp32_conv == 'miopen') else 'HIP (MFMA kernel)',
                        'fp32_conv': args.fp32_conv if dtype == torch.float32 else None,
                        'pyramid_dtype': args.pyramid_dtype},
-            'roofline': roofline_probe(B, H, W, dtype, device, feature_dtype=DT[args.pyramid_dtype] if args.pyramid_dtype else None),
         }
-        conv_rf = conv_roofline_probe(B, H, W, dtype, device, args.fp32_conv)
-        if conv_rf is not None:
-            line['roofline_conv'] = conv_rf
-        if dtype != torch.float32 or args.fp32_conv != 'miopen':
+        # --full: what the headline does not need — probes with runs of their own, the fixtures' checks, the CPU baseline
+        if args.full:
+            line['roofline'] = roofline_probe(B, H, W, dtype, device, feature_dtype=DT[args.pyramid_dtype] if args.pyramid_dtype else None)
+            conv_rf = conv_roofline_probe(B, H, W, dtype, device, args.fp32_conv)
+            if conv_rf is not None:
+                line['roofline_conv'] = conv_rf
+        if args.full and (dtype != torch.float32 or args.fp32_conv != 'miopen'):
             # the whole step against the matrix-core peak: every convolution's algorithmic flop / the
             # step time bench.py reports — the efficiency of the STEP, not of its best layer (`roofline_conv`); in the fp32 parity
             # mode the split-precision kernel spends three matrix products per operand pair, so its ceiling is a third of the peak
@@ -791,7 +836,7 @@ def main():
                                      'algorithmic_gflop_per_step': round(flop / 1e9, 1),
                                      'gflop_by_stack': {k: round(v / 1e9, 1) for k, v in parts.items()},
                                      'note': 'sum of 2*k*k*Cin*Cout*pixels over the convolutions of one step / ms_per_step; includes the memory-bound operators\' time'}
-        if world == 1 and not args.no_literal_split and not args.torch_pyramid and dtype != torch.float32 and not args.no_graph:
+        if args.full and world == 1 and not args.no_literal_split and not args.torch_pyramid and dtype != torch.float32 and not args.no_graph:
             # north_star's letter ("the feature-pyramid convolutions stay PyTorch-ROCm"): the same workload with the pyramid
             # through MIOpen, timed in this run beside the headline (which runs the pyramid on the hand-written kernel too)
             try:
@@ -829,16 +874,16 @@ def main():
                 line['literal_split'] = {'error': '%s: %s' % (type(e).__name__, e)}
         if single is not None:
             line['one_step_in_flight'] = single
-        if world == 1 and not args.no_epe_probe and (H, W) == (384, 1280):
+        if args.full and world == 1 and not args.no_epe_probe and (H, W) == (384, 1280):
             try:
                 line['epe_vs_reference'] = epe_probe(net, args.streams, not args.no_graph, device)
             except Exception as e:                            # (must never take the headline line down)
                 line['epe_vs_reference'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        if world == 1 and args.workload == 'kitti_native' and not args.no_eval_probe:
+        if args.full and world == 1 and args.workload == 'kitti_native' and not args.no_eval_probe:
             line['eval_batch1'] = eval_probe(net, H, W, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline()
-        if world == 1 and not args.no_train_probe and args.workload == 'config2':
+        if args.full and world == 1 and not args.no_train_probe and args.workload == 'config2':
             line['train_step'] = train_probe(device)
         print(json.dumps(line), flush=True)
     if world > 1:
