@@ -480,6 +480,42 @@ long long upf_conv_bias_grad_workspace_bytes(int Cout);
 int upf_conv_bias_grad(const void* grad_pre, long long g_batch_stride, float* grad_bias, void* workspace, int B, int Cout, int HW,
                        int dtype, void* stream);
 
+/* ---- gradients of the split-precision convolution: fp32 training on the fp16 matrix cores  (csrc/conv_x3_bwd.hip) ----------
+ * y = LeakyReLU_slope(conv(x, w) + b), fp32 tensors and fp32 gradients, no host synchronisation (the step captures into a hipGraph).
+ * GRADIENT RANGE.  The operand split has an absolute floor (an un-scaled operand below 2^-3 has a subnormal low half, below 6e-8 both
+ * halves are zero) and the losses are mean()-reduced: grad_pre is routinely 1e-6 ... 1e-9.  So the gradient that enters a layer's
+ * pre-activation only exists SCALED by a per-tensor power of two taken from its device-side |.|max (the rule of the packed weights:
+ * the maximum lands in [2^13, 2^14)); every consumer un-scales exactly.  Results for grad_y and grad_y * 2^-k are the same bits up
+ * to that factor.
+ *   upf_act_grad_x3   gs = grad_y * (y > 0 ? 1 : slope) * 2^s  (y NULL: no activation) over [B,C,HW] channel slices (batch strides in
+ *                     elements, 0 = dense);  scale_slot: 4 floats on the device, written {|.|max bits, 2^s, 2^-s, 0};  bias_partial
+ *                     (optional): C x 32 sums of gs, the first stage of the bias gradient, fixed order.  Three launches.
+ *   upf_conv_x3_pack_weights_dgrad   the operand of the data gradient of a stride-1 layer: upf_conv_x3_pack_weights of the flipped,
+ *                     transposed kernel (upf_conv_x3_packed_bytes(Cout, Cin, k) bytes; same header and per-layer scale).  NOT read-only
+ *                     afterwards: upf_conv_x3_dgrad rewrites one header field per call (stream ordered).
+ *   upf_conv_x3_dgrad grad_x [B,Cin,H,W] from gs [B,Cout,Ho,Wo]: stride 1 (3x3 with dilation 1..16, 1x1) = upf_conv_x3_forward on
+ *                     w_packed_dgrad, the un-scaling folded into the operand header's 2^-s (zero_bias: Cin zeros; w unused);
+ *                     stride 2 (3x3) = a plain fp32 kernel on the master weights w [Cout,Cin,3,3] (w_packed_dgrad, zero_bias unused).
+ *                     Any H, W >= 1.
+ *   upf_conv_x3_wgrad grad_w [Cout,Cin,k,k] = sum over 1..6 levels (uses of the same weights: x [B,Cin,H,W], grad_pre = gs
+ *                     [B,Cout,Ho,Wo], each with its own scale_slots[l]; NULL array = un-scaled) of the pixel sums
+ *                     gs[n,co,y,x] * x[n,ci,y*s+(ky-1)d,x*s+(kx-1)d]: both operands split into fp16 halves on the way into the
+ *                     registers, three v_mfma_f32_16x16x32_f16 per pair, K = the flattened pixels (any H, W >= 1, either stride),
+ *                     deterministic split-K (per-slice partial blocks in `workspace`, one ordered reduction that also applies each
+ *                     level's 2^-s).  grad_bias (optional) [Cout]: finished by the same reduction from bias_partials[l] (the C x 32
+ *                     buffers of upf_act_grad_x3, one per level).  Workspace: upf_conv_x3_wgrad_workspace_bytes (the size through *bytes; UPF_EINVAL for what the kernel does not take). */
+int upf_act_grad_x3(const float* grad_y, long long gy_batch_stride, const float* y, long long y_batch_stride, float* grad_pre_scaled,
+                    long long dst_batch_stride, float* bias_partial, float* scale_slot, int B, int C, int HW, float slope, void* stream);
+int upf_conv_x3_pack_weights_dgrad(const float* w, void* w_packed, int Cin, int Cout, int kernel_size, void* stream);
+int upf_conv_x3_dgrad(const float* grad_pre_scaled, long long g_batch_stride, const float* scale_slot, const float* w,
+                      void* w_packed_dgrad, const float* zero_bias, float* grad_x, long long gx_batch_stride, int B, int Cin,
+                      int Cout, int H, int W, int kernel_size, int dilation, int stride, void* stream);
+int upf_conv_x3_wgrad_workspace_bytes(const upf_wgrad_level* levels, int nlevels, int Cin, int Cout, int kernel_size,
+                                      int dilation, int stride, long long* bytes /* host, out */);
+int upf_conv_x3_wgrad(const upf_wgrad_level* levels /* host array */, const float* const* scale_slots /* host array */, int nlevels,
+                      float* grad_w, void* workspace, int Cin, int Cout, int kernel_size, int dilation, int stride,
+                      const float* const* bias_partials /* host array */, float* grad_bias, void* stream);
+
 /* ---- flow bookkeeping of a pyramid level  (model/upflow.py:566-572) -------------------------------
  * out[n,:] = cast(a + (b + c)) in fp32, b and c optional: `flow_up + res` into the context network's input,
  * `flow_up + (res + fine)` for the next level, or a plain fp32 -> 16-bit copy of a flow into an estimator slot.

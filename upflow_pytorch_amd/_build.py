@@ -21,6 +21,7 @@ SOURCES = [
     ('conv_c8.hip', []),
     ('conv_pair.hip', []),
     ('conv_x3.hip', []),
+    ('conv_x3_bwd.hip', []),
     ('conv_wgrad.hip', []),
     ('warp.hip', ['-ffp-contract=off']),
     ('sgu_blend.hip', ['-ffp-contract=off']),

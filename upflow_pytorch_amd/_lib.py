@@ -61,6 +61,11 @@ SIGNATURES = {
     'upf_conv_x3_pack_weights': [_vp, _vp, _i, _i, _i, _vp],
     'upf_conv_x3_forward': [_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
     'upf_mfma_f16_denorm_probe': [_vp, _vp],
+    'upf_act_grad_x3': [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp],
+    'upf_conv_x3_pack_weights_dgrad': [_vp, _vp, _i, _i, _i, _vp],
+    'upf_conv_x3_dgrad': [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    'upf_conv_x3_wgrad_workspace_bytes': [_vp, _i, _i, _i, _i, _i, _i, _c.POINTER(_ll)],
+    'upf_conv_x3_wgrad': [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     'upf_conv_pack_weights_f32': [_vp, _vp, _i, _i, _i, _i, _i, _vp],
     'upf_conv_pack_stacked_dgrad': [_c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i, _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i, _i, _vp],
     'upf_conv_pack_weights_f32_multi': [_c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i, _i, _vp],

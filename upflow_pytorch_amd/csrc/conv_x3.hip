@@ -23,7 +23,7 @@
 // too); the epilogue adds nothing (the accumulators start at the bias), applies LeakyReLU and stores fp32.
 #include <cstring>
 #include <cstdint>
-#include "conv_kernel.hpp"
+#include "conv_x3_common.hpp"
 
 // Ablation switches for tools/x3_ablate.hip (always 0 in the library): 1 = no matrix phase, 2 = no split / transposition / LDS
 // stores (the loaded values are only kept alive), 4 = no global loads of the tile, 8 = the matrix phase multiplies registers
@@ -39,19 +39,6 @@ using namespace upf::conv;
 constexpr int TH = 8;                    // tile rows
 static int g_sk_max_tiles = 96;          // split-K kernel where the image has at most this many 8 x 32 tiles (upf_conv_x3_set_option)
 constexpr int NOCT = 2;                  // channel octets per chunk (16 input channels)
-
-__host__ __device__ constexpr int pad16(int v) { return (v + 15) / 16 * 16; }
-
-// 8 consecutive fp32 pixels of one channel row -> 4 dwords of fp16 hi halves, 4 dwords of fp16 lo halves
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-#pragma unroll
-  for (int pp = 0; pp < 4; ++pp) {
-    const uint32_t h = pack2<f16_t>(v[2 * pp], v[2 * pp + 1]);
-    const float r0 = v[2 * pp] - f16_bits_to_f32(h & 0xffffu), r1 = v[2 * pp + 1] - f16_bits_to_f32(h >> 16);
-    hi[pp] = h;
-    lo[pp] = pack2<f16_t>(r0, r1);
-  }
-}
 
 // 4 consecutive fp32 pixels of one channel row -> 2 dwords of fp16 hi halves, 2 dwords of fp16 lo halves
 __device__ __forceinline__ void split4(const f32x4& v, u32x2& hi, u32x2& lo) {
@@ -87,7 +74,6 @@ __device__ __forceinline__ void stage_store_half(uint4* tile, int enc, int half,
 // not the dropped lo*lo product, not the accumulation chain — was the whole error of the first form of this kernel (per-layer rms
 // 8.7e-7 vs fp64, reproduced on the CPU with exact accumulation).  Scaled, the low halves are normal numbers with their own 11
 // bits.  The kernel starts its accumulators at bias * 2^s and multiplies the result by 2^-s in the epilogue: both exact.
-constexpr int HDR_F16 = 512;                          // header size in fp16 elements (1 KB)
 __global__ void x3_hdr_zero_kernel(uint32_t* hdr) { if (threadIdx.x < 256) hdr[threadIdx.x] = 0u; }
 __global__ void x3_absmax_kernel(const float* __restrict__ w, long long n, uint32_t* hdr) {
   float m = 0.f;
@@ -98,14 +84,6 @@ __global__ void x3_absmax_kernel(const float* __restrict__ w, long long n, uint3
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
   if ((threadIdx.x & 63) == 0) atomicMax(hdr, __float_as_uint(m));           // non-negative floats order like their bit patterns
-}
-__device__ __forceinline__ float x3_scale_of(uint32_t absmax_bits) {
-  const float m = __uint_as_float(absmax_bits);
-  if (!(m > 0.f) || m > 3.0e38f) return 1.f;
-  int e = (int)((absmax_bits >> 23) & 0xffu) - 127;   // floor(log2(m)) for normal m (a subnormal maximum: e = -127, clamped below)
-  int sft = 13 - e;
-  sft = sft > 100 ? 100 : (sft < -100 ? -100 : sft);
-  return __uint_as_float((uint32_t)(127 + sft) << 23);
 }
 __global__ void pack_x3_kernel(const float* __restrict__ w, f16_t* __restrict__ wp, int Cin, int Cout, int ntaps) {
   const int cip = pad16(Cin), cop = pad32(Cout), nk = cip / 16;
@@ -570,6 +548,12 @@ __global__ void mfma_f16_denorm_probe_kernel(float* out) {
   if (threadIdx.x == 0) out[0] = c[0];
 }
 
+// the first two launches of both packers: zero the header, |w|max bits into header[0]
+void launch_header_absmax(const float* w, long long nw, void* w_packed, hipStream_t stream) {
+  hipLaunchKernelGGL(x3_hdr_zero_kernel, dim3(1), dim3(256), 0, stream, (uint32_t*)w_packed);
+  hipLaunchKernelGGL(x3_absmax_kernel, dim3((unsigned)((nw + 255) / 256 > 1024 ? 1024 : (nw + 255) / 256)), dim3(256), 0, stream, w, nw, (uint32_t*)w_packed);
+}
+
 }  // namespace convx3
 }  // namespace upf
 
@@ -585,8 +569,7 @@ extern "C" int upf_conv_x3_pack_weights(const float* w, void* w_packed, int Cin,
   const long long total = (long long)ntaps * conv::pad32(Cout) * convx3::pad16(Cin) * 2;
   const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
   const long long nw = (long long)Cout * Cin * ntaps;
-  hipLaunchKernelGGL(convx3::x3_hdr_zero_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (uint32_t*)w_packed);
-  hipLaunchKernelGGL(convx3::x3_absmax_kernel, dim3((unsigned)((nw + 255) / 256 > 1024 ? 1024 : (nw + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, nw, (uint32_t*)w_packed);
+  convx3::launch_header_absmax(w, nw, w_packed, (hipStream_t)stream);
   hipLaunchKernelGGL(convx3::pack_x3_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (f16_t*)w_packed, Cin, Cout, ntaps);
   return check_launch("conv_x3_pack_weights");
 }

@@ -473,6 +473,9 @@ def fast_conv_seq(seq, x, cache, out=None, allow_hip=True, pitched=False):
         return pc(x, y)
     if torch.is_grad_enabled() and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and c.weight.dtype == torch.float32:
         y = train_conv_seq(seq, x)                       # training on the matrix cores: 16-bit activations, fp32 master weights
+    elif (FP32_TRAIN_CONV[0] == 'hip_x3' and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+          and c.weight.dtype == torch.float32):
+        y = train_conv_seq_x3(seq, x)                    # the fp32 step on the matrix cores in split precision: no PyTorch-ROCm convolution
     else:
         y = seq(x if x.is_contiguous() else x.contiguous())
     if out is not None:
@@ -499,6 +502,43 @@ def train_conv_seq(seq, x):
             and ops.conv_train_supported(x, c.weight, c.stride[0], c.dilation[0])):
         return ops.conv_train(x, c.weight, c.bias, c.dilation[0], slope, c.stride[0])
     return seq(x.float()).to(x.dtype)
+
+
+def train_conv_seq_x3(seq, x):
+    """One `conv(...)` Sequential under autograd in fp32 through ops.ConvX3TrainFunction (config `fp32_train_conv = 'hip_x3'`):
+    forward, data gradient and weight gradient on the split-precision MFMA kernels, any H, W.  There is no fallback: a layer the
+    kernels do not take is an error."""
+    c = seq[0]
+    k = c.kernel_size[0]
+    slope = 0.0
+    for m in list(seq)[1:]:
+        if not isinstance(m, nn.LeakyReLU):
+            raise ops.UpflowHipError("fp32_train_conv='hip_x3': conv(...) Sequentials of Conv2d [+ LeakyReLU] only, got %s" % type(m).__name__)
+        slope = float(m.negative_slope)
+    if not (c.kernel_size in ((3, 3), (1, 1)) and c.stride[0] == c.stride[1] and c.groups == 1 and c.padding == (((k - 1) * c.dilation[0]) // 2,) * 2
+            and c.dilation[0] == c.dilation[1] and c.padding_mode == 'zeros'):
+        raise ops.UpflowHipError("fp32_train_conv='hip_x3': unsupported convolution %r" % (c,))
+    return ops.conv_x3_train(x, c.weight, c.bias, c.dilation[0], slope, c.stride[0])
+
+
+# fp32 TRAINING (train_conv_dtype = 'fp32'): 'miopen' = every convolution under autograd through PyTorch-ROCm (the default),
+# 'hip_x3' = ops.ConvX3TrainFunction.  Set by UPFlow_net for the duration of a forward (config `fp32_train_conv`).
+FP32_TRAIN_CONV = ['miopen']
+FP32_TRAIN_CONV_MODES = ('miopen', 'hip_x3')
+
+
+class fp32_train_conv_mode(object):
+    def __init__(self, mode):
+        if mode not in FP32_TRAIN_CONV_MODES:
+            raise ValueError("fp32_train_conv must be one of %s, got %r" % (list(FP32_TRAIN_CONV_MODES), mode))
+        self.mode = mode
+
+    def __enter__(self):
+        self.saved = FP32_TRAIN_CONV[0]
+        FP32_TRAIN_CONV[0] = self.mode
+
+    def __exit__(self, *exc):
+        FP32_TRAIN_CONV[0] = self.saved
 
 
 # fp32 inference (the parity mode): 'hip_x3' = the split-precision matrix-core kernel (csrc/conv_x3.hip, 3 fp16 products per

@@ -8,7 +8,8 @@ What is native here (one hand-written HIP launch each, csrc/*.hip):
     cost volume (+LeakyReLU, written straight into the estimator's 115-channel input buffer),
     backward warp (+validity mask), flow up-sampling (+rescale), SGU interpolation-blend,
     feature normalisation, occlusion check.
-Convolutions: fp32 (the parity mode) and everything under autograd stay PyTorch-ROCm (MIOpen); in bf16/fp16
+Convolutions: fp32 under autograd is PyTorch-ROCm (MIOpen) by default and the split-precision MFMA kernels with
+`fp32_train_conv='hip_x3'`; in bf16/fp16
 inference the flow-estimator / context / SGU-estimator convolutions run on the hand-written MFMA kernel
 (csrc/conv3x3.hip), and so do the feature-pyramid and 1x1 convolutions unless
 `hip_pyramid_convs=False` restores the north star's literal split ("the feature-pyramid convolutions stay
@@ -18,9 +19,18 @@ while flows, sampling positions, masks, normalisation statistics and all accumul
 Extra (non-reference) config flags, all defaulting to the reference's behaviour:
     warp_mask_mode = 'literal' | 'robust'   validity-mask semantics of the feature warps (§7-H2)
     hip_pyramid_convs = True | False        16-bit inference: feature pyramid on the MFMA kernel / on MIOpen
-    train_conv_dtype = 'fp32' | 'bf16' | 'fp16'   training: 'fp32' = the parity mode (every convolution PyTorch-ROCm);
+    train_conv_dtype = 'fp32' | 'bf16' | 'fp16'   training: 'fp32' = the parity mode (fp32 activations and gradients; its
+                                            convolutions are chosen by fp32_train_conv);
                                             16-bit = decoder activations in that type, fp32 master weights, forward /
                                             data-gradient / weight-gradient of the decoder convolutions on the MFMA kernels
+    fp32_train_conv = 'miopen' | 'hip_x3'   the convolutions of the fp32 training step: 'miopen' (default) = PyTorch-ROCm forward
+                                            and backward; 'hip_x3' = ops.ConvX3TrainFunction for EVERY nn.Conv2d of the network —
+                                            split-precision products on the fp16 matrix cores (csrc/conv_x3.hip, conv_x3_bwd.hip),
+                                            the gradient entering each pre-activation scaled by a per-tensor power of two from
+                                            its device-side maximum and un-scaled exactly; no PyTorch-ROCm convolution, any
+                                            H, W, bit-reproducible.  The stacked schedule only (`stacked_training = True`, the
+                                            default): the reference's per-direction schedule raises UpflowHipError under grad with
+                                            this mode instead of falling back.  Anything else raises ValueError.
 """
 import os
 import torch
@@ -260,6 +270,7 @@ class UPFlow_net(tools.abstract_model):
             self.hip_pyramid_convs = True
             self.train_conv_dtype = 'fp32'          # 'bf16' / 'fp16': decoder convolutions under autograd on the matrix cores
             self.fp32_conv = 'hip_x3'               # fp32 inference: 'hip_x3' / 'hip_x3s' split-precision MFMA kernel, 'miopen' PyTorch-ROCm
+            self.fp32_train_conv = 'miopen'         # fp32 training: 'miopen' PyTorch-ROCm, 'hip_x3' split-precision MFMA kernels under autograd
             self.fp16_overflow_check = False        # fp16 features / activations: raise if an output is not finite (one reduction + a host sync per forward)
 
         def __call__(self, ):
@@ -268,6 +279,8 @@ class UPFlow_net(tools.abstract_model):
     def __init__(self, conf: config):
         super(UPFlow_net, self).__init__()
         self.conf = conf
+        from .pwc_modules import fp32_train_conv_mode
+        fp32_train_conv_mode(getattr(conf, 'fp32_train_conv', 'miopen'))      # (ValueError for an unknown mode)
         if conf.if_use_cor_pytorch:
             raise ops.UpflowHipError(
                 "if_use_cor_pytorch=True selects the reference's CPU fallback (utils/pytorch_correlation.py); "
@@ -401,8 +414,12 @@ class UPFlow_net(tools.abstract_model):
     def forward_2_frame_v3(self, x1_raw, x2_raw, if_loss=False):
         """Coarse-to-fine bidirectional decode, model/upflow.py:494-533."""
         cdt = self.feature_pyramid_extractor.convs[0][0][0].weight.dtype      # compute dtype of the convs (of the PYRAMID: to_inference)
-        from .pwc_modules import fp32_conv_mode
-        with fp32_conv_mode(getattr(self.conf, 'fp32_conv', 'hip_x3')):
+        from .pwc_modules import fp32_conv_mode, fp32_train_conv_mode
+        tmode = getattr(self.conf, 'fp32_train_conv', 'miopen')
+        if getattr(self.conf, 'train_conv_dtype', 'fp32') != 'fp32':
+            fp32_train_conv_mode(tmode)                 # (validated; the 16-bit training path has its own convolutions)
+            tmode = 'miopen'
+        with fp32_conv_mode(getattr(self.conf, 'fp32_conv', 'hip_x3')), fp32_train_conv_mode(tmode):
             return self._forward_2_frame_v3(x1_raw, x2_raw, if_loss, cdt)
 
     def _forward_2_frame_v3(self, x1_raw, x2_raw, if_loss, cdt):
@@ -437,6 +454,9 @@ class UPFlow_net(tools.abstract_model):
                 with ops.shared_conv_grads(convs):
                     return self._forward_stacked(X.to(tdt), B, tdt)
             return self._forward_stacked(X, B)
+        from . import pwc_modules as _pm
+        if _pm.FP32_TRAIN_CONV[0] != 'miopen' and torch.is_grad_enabled():
+            raise ops.UpflowHipError("fp32_train_conv='hip_x3' runs the stacked schedule only (stacked_training = True)")
         x1_raw = x1_raw.to(cdt)
         x2_raw = x2_raw.to(cdt)
         x1_pyramid = self.feature_pyramid_extractor(x1_raw)

@@ -1405,6 +1405,7 @@ def conv_pack_from_master(weight32, dtype, dgrad=False):
 
 def conv_pack_cache_clear():
     _PACK_CACHE.clear()
+    _X3_TRAIN_CACHE.clear()
 
 
 # The packed 16-bit weight copies (here and in model/pwc_modules._PackedConv*) and runtime.GraphedInference's staleness check are
@@ -1510,6 +1511,7 @@ def _train_cache_tensors():
         out.extend(slot[1].values())
     out.extend(v[2] for v in _S2D_CACHE.values())
     out.extend(v[2] for v in _STACK_PACK_CACHE.values())
+    out.extend(v[2] for v in _X3_TRAIN_CACHE.values())
     out.extend(_ZERO_BIAS.values())
     return out
 
@@ -1544,7 +1546,7 @@ def train_caches_after_capture(mark):
             del d[k]
         if not d:
             del _PACK_CACHE[wid]
-    for cache in (_S2D_CACHE, _STACK_PACK_CACHE):
+    for cache in (_S2D_CACHE, _STACK_PACK_CACHE, _X3_TRAIN_CACHE):
         for k in [k for k, v in cache.items() if not _marked(mark, v[2])]:
             del cache[k]
     return keep
@@ -1558,6 +1560,7 @@ def train_caches_clear():
     _PACK_CACHE.clear()
     _S2D_CACHE.clear()
     _STACK_PACK_CACHE.clear()
+    _X3_TRAIN_CACHE.clear()
 
 
 def _conv_pack_from_master(weight32, dtype, dgrad=False):
@@ -1947,6 +1950,154 @@ class ConvTrainFunction(Function):
 def conv_train(x, weight, bias, dilation=1, slope=0.0, stride=1):
     w, b, sink = _gated(weight, bias)
     return ConvTrainFunction.apply(x, w, b, dilation, slope, stride, sink)
+
+
+# ---- the fp32 training step on the matrix cores: split-precision convolutions under autograd (csrc/conv_x3_bwd.hip) -------------
+_X3_TRAIN_CACHE = {}         # (id(master), dgrad) -> ((version, data_ptr), weakref, packed operand)
+
+
+def conv_x3_pack_from_master(weight32, dgrad=False):
+    """fp32 master weights [Cout,Cin,k,k] -> the split-precision kernel's packed fp16 hi / lo operand, for the forward convolution
+    or (dgrad) for the data gradient of a stride-1 layer (flipped, transposed kernel).  Cached per parameter VERSION like
+    conv_pack_from_master; cleared by conv_pack_cache_clear / train_caches_clear."""
+    key = (weight32._version, weight32.data_ptr())
+    slot = _X3_TRAIN_CACHE.get((id(weight32), bool(dgrad)))
+    if slot is not None and slot[0] == key and slot[1]() is weight32:
+        return slot[2]
+    w = weight32.detach()
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        raise UpflowHipError('conv_x3_train: contiguous fp32 master weights expected')
+    Cout, Cin, k, k2 = w.shape
+    if k != k2 or k not in (1, 3):
+        raise UpflowHipError('conv_x3_train: 3x3 or 1x1 kernels only')
+    dev = _lib.check_gpu(w)
+    nbytes = _lib.lib().upf_conv_x3_packed_bytes(Cout if dgrad else Cin, Cin if dgrad else Cout, k)
+    packed = torch.empty((nbytes // 2,), dtype=torch.float16, device=w.device)
+    with torch.cuda.device(dev):
+        _lib.call('upf_conv_x3_pack_weights_dgrad' if dgrad else 'upf_conv_x3_pack_weights', _lib.ptr(w), _lib.ptr(packed), Cin, Cout, k,
+                  _lib.stream_ptr(dev))
+    if len(_X3_TRAIN_CACHE) > 4096:
+        _X3_TRAIN_CACHE.clear()
+    _X3_TRAIN_CACHE[(id(weight32), bool(dgrad))] = (key, weakref.ref(weight32), packed)
+    return packed
+
+
+def act_grad_x3(gy, y=None, slope=0.0, want_bias=False):
+    """fp32 [B,C,H,W] channel slices: gs = gy * (y > 0 ? 1 : slope) * 2^s (y None: no activation), 2^s the power of two that puts
+    max |gs| into [2^13, 2^14), taken on the device (upf_act_grad_x3).  -> (gs, scale slot [4] = {max bits, 2^s, 2^-s, 0},
+    first-stage bias sums [C,32] of gs or None)."""
+    B, C, H, W = gy.shape
+    for t in (gy, y):
+        if t is not None and (not _is_slice(t) or tuple(t.shape) != (B, C, H, W) or t.dtype != torch.float32):
+            raise UpflowHipError('act_grad_x3: operands must be fp32 [B,C,H,W] channel slices of one shape')
+    dev = _lib.check_gpu(gy, y, contiguous=False)
+    gs = torch.empty((B, C, H, W), dtype=torch.float32, device=gy.device)
+    slot = torch.empty((4,), dtype=torch.float32, device=gy.device)
+    part = torch.empty((C, 32), dtype=torch.float32, device=gy.device) if want_bias else None
+    with torch.cuda.device(dev):
+        _lib.call('upf_act_grad_x3', _lib.ptr(gy), gy.stride(0), _lib.ptr(y), y.stride(0) if y is not None else 0, _lib.ptr(gs), gs.stride(0),
+                  _lib.ptr(part), _lib.ptr(slot), B, C, H * W, float(slope), _lib.stream_ptr(dev))
+    return gs, slot, part
+
+
+def conv_x3_dgrad(gs, slot, weight32, x_shape, dilation=1, stride=1):
+    """Data gradient [B,Cin,H,W] (fp32) of the split-precision convolution from the SCALED pre-activation gradient (act_grad_x3).
+    Stride 1 writes the gradient's 2^-s into the header of the cached, shared packed dgrad operand of `weight32` just before the
+    convolution reads it: all data gradients of one parameter must be enqueued on ONE stream (a captured step: one capture
+    stream, no parallel branches that share a weight).  The Trainer and autograd's single backward stream satisfy this."""
+    Cout, Cin, k, _ = weight32.shape
+    B, _, H, W = x_shape
+    dev = _lib.check_gpu(gs, slot, weight32)
+    gx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=gs.device)
+    w = weight32.detach()
+    packed = conv_x3_pack_from_master(weight32, dgrad=True) if stride == 1 else None
+    zb = _zero_bias(gs.device, Cin) if stride == 1 else None
+    with torch.cuda.device(dev):
+        _lib.call('upf_conv_x3_dgrad', _lib.ptr(gs), gs.stride(0), _lib.ptr(slot), _lib.ptr(w), _lib.ptr(packed), _lib.ptr(zb), _lib.ptr(gx),
+                  gx.stride(0), B, Cin, Cout, H, W, k, int(dilation) if k == 3 else 1, int(stride), _lib.stream_ptr(dev))
+    return gx
+
+
+def conv_x3_wgrad(uses, Cin, Cout, k, dilation=1, stride=1, want_bias=False):
+    """fp32 weight gradient [Cout,Cin,k,k] over 1..6 uses [(x, gs, slot, bias_part), ...] of one convolution (x: [B,Cin,H,W] fp32
+    slices, gs / slot / bias_part from act_grad_x3): K = the pixels of all uses, deterministic split-K, and — want_bias — the bias
+    gradient [Cout] from the same reduction launch (upf_conv_x3_wgrad).  -> (grad_w, grad_b or None)"""
+    import ctypes
+    if not 1 <= len(uses) <= 6:
+        raise UpflowHipError('conv_x3_wgrad: 1..6 uses')
+    dev = uses[0][0].device
+    d = int(dilation) if k == 3 else 1
+    arr = (_lib.WgradLevel * len(uses))()
+    for a, (x, g, slot, part) in zip(arr, uses):
+        B, _, H, W = x.shape
+        Ho, Wo = conv3x3_out_hw(H, W, stride)
+        if (not _is_slice(x) or not _is_slice(g) or x.shape[1] != Cin or tuple(g.shape) != (B, Cout, Ho, Wo)
+                or x.dtype != torch.float32 or g.dtype != torch.float32):
+            raise UpflowHipError('conv_x3_wgrad: x [B,%d,H,W] and g [B,%d,Ho,Wo] fp32 channel slices expected' % (Cin, Cout))
+        _lib.check_gpu(x, g, slot, part, contiguous=False)
+        a.x, a.x_batch_stride, a.grad_pre, a.g_batch_stride = x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0)
+        a.B, a.H, a.W = B, H, W
+    nbytes = ctypes.c_longlong(0)
+    _lib.call('upf_conv_x3_wgrad_workspace_bytes', arr, len(uses), Cin, Cout, k, d, int(stride), ctypes.byref(nbytes))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    gw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=dev)
+    gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if want_bias else None
+    slots = (ctypes.c_void_p * len(uses))(*[u[2].data_ptr() for u in uses])
+    parts = (ctypes.c_void_p * len(uses))(*[u[3].data_ptr() for u in uses]) if want_bias else None
+    with torch.cuda.device(dev):
+        _lib.call('upf_conv_x3_wgrad', arr, slots, len(uses), _lib.ptr(gw), _lib.ptr(ws), Cin, Cout, k, d, int(stride), parts, _lib.ptr(gb),
+                  _lib.stream_ptr(dev))
+    return gw, gb
+
+
+class ConvX3TrainFunction(Function):
+    """y = LeakyReLU_slope(conv2d(x, weight, bias, padding = dilation * (k-1)/2, dilation, stride)) with fp32 activations, fp32
+    master weights and fp32 gradients, every product on the fp16 matrix cores in split precision (three products per operand
+    pair): forward csrc/conv_x3.hip, backward csrc/conv_x3_bwd.hip — the gradient entering the pre-activation is scaled by a
+    per-tensor power of two taken from its device-side maximum (act_grad_x3) and un-scaled exactly by its consumers.  No
+    PyTorch-ROCm convolution, no host synchronisation, bit-reproducible.  slope 0 = no activation.  3x3 (dilation 1..16 at
+    stride 1, dilation 1 at stride 2) or 1x1 at stride 1; any H, W >= 1."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dilation, slope, stride):
+        if not _is_slice(x):
+            x = x.contiguous()
+        Cout, Cin, k, _ = weight.shape
+        B, _, H, W = x.shape
+        _lib.check_gpu(x, weight, contiguous=False)
+        if x.dtype != torch.float32 or weight.dtype != torch.float32:
+            raise UpflowHipError('conv_x3_train: fp32 activations and fp32 weights expected')
+        if not (k in (1, 3) and 1 <= dilation <= 16 and (stride == 1 or (stride == 2 and dilation == 1 and k == 3)) and x.shape[1] == Cin):
+            raise UpflowHipError('conv_x3_train: unsupported geometry (k=%d dilation=%d stride=%d)' % (k, dilation, stride))
+        Ho, Wo = conv3x3_out_hw(H, W, stride)
+        y = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+        b32 = bias.detach().contiguous() if bias is not None else _zero_bias(x.device, Cout)
+        conv3x3_forward_raw(x, conv_x3_pack_from_master(weight), b32, y, dilation, slope, stride, k)
+        ctx.save_for_backward(x, weight, y if slope != 0.0 else None)
+        ctx.cfg = (int(dilation), float(slope), bias is not None, int(stride))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        dilation, slope, has_bias, stride = ctx.cfg
+        Cout, Cin, k, _ = weight.shape
+        if gy.dtype != torch.float32 or not _is_slice(gy):
+            gy = gy.float().contiguous()
+        want_b = has_bias and ctx.needs_input_grad[2]
+        gs, slot, part = act_grad_x3(gy, y, slope, want_bias=want_b)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = conv_x3_dgrad(gs, slot, weight, x.shape, dilation, stride)
+        if ctx.needs_input_grad[1] or want_b:
+            gw, gb = conv_x3_wgrad([(x, gs, slot, part)], Cin, Cout, k, dilation, stride, want_bias=want_b)
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        return gx, gw, gb, None, None, None
+
+
+def conv_x3_train(x, weight, bias, dilation=1, slope=0.0, stride=1):
+    return ConvX3TrainFunction.apply(x, weight, bias, int(dilation), float(slope), int(stride))
 
 
 # ---- a whole dense stack (conv1..conv5 + conv_last) under autograd, in ONE buffer ---------------------------------------
