@@ -486,7 +486,17 @@ int upf_conv_bias_grad(const void* grad_pre, long long g_batch_stride, float* gr
  * halves are zero) and the losses are mean()-reduced: grad_pre is routinely 1e-6 ... 1e-9.  So the gradient that enters a layer's
  * pre-activation only exists SCALED by a per-tensor power of two taken from its device-side |.|max (the rule of the packed weights:
  * the maximum lands in [2^13, 2^14)); every consumer un-scales exactly.  Results for grad_y and grad_y * 2^-k are the same bits up
- * to that factor.
+ * to that factor, as long as the scale's exponent stays inside its clamp of +-100 (2^-87 <= max |grad_pre| < 2^114); beyond it the
+ * scale is 2^+-100, for an all-zero or non-finite maximum 1 (NaN elements do not define the maximum; NaN and inf propagate).
+ * Two floors remain (tests/test_hip_conv_x3_bwd_ops.py, modelled in tests/_x3_model.py):
+ *   - ONE scale per tensor: an element of grad_pre below 2^-16 of the tensor's maximum (|gs| < 2^-3) has a subnormal low half and
+ *     carries up to 2^-25 of absolute error in gs, i.e. 2^-38 * max |grad_pre|: grad_x (stride 1) is off by up to that times
+ *     max_ci sum_{co,tap} |w|, a row of grad_w by up to that times sum_{n,pixel} |x[n,ci]|.  Down to 2^-14 of the maximum whole regions
+ *     (an occluded half, one sample, a group of channels) keep fp32-class error relative to their OWN maximum; below, the floor.
+ *     The stride-2 data gradient (plain fp32) and the bias gradient have no such floor.
+ *   - the ACTIVATION operand of upf_conv_x3_wgrad is split un-scaled, like the forward's: |x| < 2^-3 carries up to 2^-25 of
+ *     absolute error, grad_w up to 2^-25 * max_co sum_{n,pixel} |grad_pre[n,co]|.  fp32-class for O(1) activations and above (up to
+ *     fp16's range), a floor for tiny ones.
  *   upf_act_grad_x3   gs = grad_y * (y > 0 ? 1 : slope) * 2^s  (y NULL: no activation) over [B,C,HW] channel slices (batch strides in
  *                     elements, 0 = dense);  scale_slot: 4 floats on the device, written {|.|max bits, 2^s, 2^-s, 0};  bias_partial
  *                     (optional): C x 32 sums of gs, the first stage of the bias gradient, fixed order.  Three launches.
@@ -498,7 +508,8 @@ int upf_conv_bias_grad(const void* grad_pre, long long g_batch_stride, float* gr
  *                     stride 2 (3x3) = a plain fp32 kernel on the master weights w [Cout,Cin,3,3] (w_packed_dgrad, zero_bias unused).
  *                     Any H, W >= 1.
  *   upf_conv_x3_wgrad grad_w [Cout,Cin,k,k] = sum over 1..6 levels (uses of the same weights: x [B,Cin,H,W], grad_pre = gs
- *                     [B,Cout,Ho,Wo], each with its own scale_slots[l]; NULL array = un-scaled) of the pixel sums
+ *                     [B,Cout,Ho,Wo], each with its own scale_slots[l]; NULL array or NULL entry = that grad_pre is
+ *                     UN-SCALED and taken as it is: for O(1) gradients only, the split's absolute floor applies) of the pixel sums
  *                     gs[n,co,y,x] * x[n,ci,y*s+(ky-1)d,x*s+(kx-1)d]: both operands split into fp16 halves on the way into the
  *                     registers, three v_mfma_f32_16x16x32_f16 per pair, K = the flattened pixels (any H, W >= 1, either stride),
  *                     deterministic split-K (per-slice partial blocks in `workspace`, one ordered reduction that also applies each

@@ -6,7 +6,8 @@
 //      weights), plus the first stage of the bias gradient (sums of gs).  The "slot" {|.|max bits, 2^s, 2^-s, 0} stays on the device.
 //      WHY: the split a = fp16(a) + fp16(a - fp16(a)) has an absolute floor — below 2^-3 the low half is subnormal, below 6e-8
 //      both halves are zero — and the losses are mean()-reduced, so grad_pre is routinely 1e-6 ... 1e-9.  Scaled, everything down
-//      to 2^-16 of the tensor's maximum keeps 22 bits.  Powers of two only: scaling and un-scaling are exact, so the results for
+//      to 2^-16 of the tensor's maximum keeps 22 bits (below: up to 2^-38 * max of absolute error per element, the floor stated in
+//      include/upflow_hip.h, GRADIENT RANGE; the activations of the weight gradient are split un-scaled).  Powers of two only: scaling and un-scaling are exact, so the results for
 //      grad_y and grad_y * 2^-k are the same bits up to the factor (tests/test_hip_conv_x3_train.py).  No host synchronisation.
 //   2. data gradient, stride 1 (upf_conv_x3_dgrad): upf_conv_x3_forward of gs with the flipped, transposed kernel
 //      (upf_conv_x3_pack_weights_dgrad).  The forward kernel multiplies its sums by the header's 2^-s_w; a one-thread launch sets

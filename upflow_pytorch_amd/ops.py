@@ -2021,7 +2021,9 @@ def conv_x3_dgrad(gs, slot, weight32, x_shape, dilation=1, stride=1):
 def conv_x3_wgrad(uses, Cin, Cout, k, dilation=1, stride=1, want_bias=False):
     """fp32 weight gradient [Cout,Cin,k,k] over 1..6 uses [(x, gs, slot, bias_part), ...] of one convolution (x: [B,Cin,H,W] fp32
     slices, gs / slot / bias_part from act_grad_x3): K = the pixels of all uses, deterministic split-K, and — want_bias — the bias
-    gradient [Cout] from the same reduction launch (upf_conv_x3_wgrad).  -> (grad_w, grad_b or None)"""
+    gradient [Cout] from the same reduction launch (upf_conv_x3_wgrad).  A use whose slot is None holds an UN-SCALED grad_pre (taken as
+    it is, no 2^-s: for O(1) gradients only — the split's absolute floor applies); its bias_part, if any, holds sums of that
+    un-scaled grad_pre.  -> (grad_w, grad_b or None)"""
     import ctypes
     if not 1 <= len(uses) <= 6:
         raise UpflowHipError('conv_x3_wgrad: 1..6 uses')
@@ -2042,7 +2044,7 @@ def conv_x3_wgrad(uses, Cin, Cout, k, dilation=1, stride=1, want_bias=False):
     ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
     gw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=dev)
     gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if want_bias else None
-    slots = (ctypes.c_void_p * len(uses))(*[u[2].data_ptr() for u in uses])
+    slots = None if all(u[2] is None for u in uses) else (ctypes.c_void_p * len(uses))(*[u[2].data_ptr() if u[2] is not None else None for u in uses])
     parts = (ctypes.c_void_p * len(uses))(*[u[3].data_ptr() for u in uses]) if want_bias else None
     with torch.cuda.device(dev):
         _lib.call('upf_conv_x3_wgrad', arr, slots, len(uses), _lib.ptr(gw), _lib.ptr(ws), Cin, Cout, k, d, int(stride), parts, _lib.ptr(gb),
