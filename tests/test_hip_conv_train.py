@@ -488,3 +488,85 @@ def test_conv_prepack_fills_the_caches_the_layers_read():
         ops._conv_pack_from_master = real
     assert calls['n'] == 0                                  # every operand came out of the one prepack launch
     assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]) and not torch.equal(got[0], want[0])
+
+
+def test_operand_cache_serves_every_form_and_follows_the_parameters(monkeypatch):
+    """Every operand form of the one training cache (ops._OPERANDS) through the public functions — conv_train at stride 1 (forward,
+    data gradient) and stride 2 (space-to-depth data gradient), conv_x3_train, a dense stack (stacked data-gradient operands): a
+    warm run packs nothing and repeats the cold one bit for bit; after an in-place update of the weights the results are those of
+    a run from an empty cache (and others than before); after conv_prepack no layer packs its own operand."""
+    from upflow_pytorch_amd import _lib, ops
+    packs, real = [], _lib.call
+
+    def counting(name, *args):
+        if name.startswith(('upf_conv_pack', 'upf_conv_x3_pack')):          # (upf_conv_pack_stacked_dgrad among them)
+            packs.append(name)
+        return real(name, *args)
+    monkeypatch.setattr(_lib, 'call', counting)
+    g = torch.Generator().manual_seed(21)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+
+    def conv_layer(fn, x, Cout, stride):
+        w = (rnd(Cout, x.shape[1], 3, 3) * 0.1).cuda().requires_grad_(True)
+        b = (rnd(Cout) * 0.1).cuda().requires_grad_(True)
+        gy = rnd(x.shape[0], Cout, *ops.conv3x3_out_hw(x.shape[2], x.shape[3], stride)).to(x.dtype).cuda()
+
+        def run():
+            y = fn(x, w, b, 1, 0.1, stride)
+            return (y.detach().clone(),) + torch.autograd.grad(y, (x, w, b), gy)
+        return [w], run
+
+    x16 = rnd(1, 8, 8, 16).bfloat16().cuda().requires_grad_(True)
+    x32 = rnd(1, 8, 5, 7).cuda().requires_grad_(True)
+    B, H, W = 1, 4, 13
+    m = _dense_stack(115, 'cuda')
+    c, A = (rnd(B, ch, H, W).bfloat16().cuda().requires_grad_(True) for ch in (81, 32))
+    flow = rnd(B, 2, H, W).cuda().requires_grad_(True)
+    g_buf, g_out = (rnd(B, m._n_total + 2, H, W) * 0.1).bfloat16().cuda(), rnd(B, 2, H, W).bfloat16().cuda()
+    assert m.train_in_buffer_ok([c, A, flow])
+
+    def run_stack():
+        buf, out = m.forward_train([c, A, flow], flow_tail=flow)
+        return (buf.detach().clone(),) + torch.autograd.grad((buf, out), [c, A, flow] + list(m.parameters()), (g_buf, g_out)) + (out.detach().clone(),)
+
+    layers = {'stride1': conv_layer(ops.conv_train, x16, 16, 1), 'stride2': conv_layer(ops.conv_train, x16, 16, 2),
+              'x3': conv_layer(ops.conv_x3_train, x32, 16, 1), 'stack': ([p for p in m.parameters() if p.dim() == 4], run_stack)}
+    assert ops._s2d_ok(x16, layers['stride2'][0][0], 2, 1)
+    same = lambda u, v: len(u) == len(v) and all(torch.equal(a, b) for a, b in zip(u, v))
+    want_packs = {'stride1': ['upf_conv_pack_weights_f32'] * 2, 'stride2': ['upf_conv_pack_weights_f32'] * 2,
+                  'x3': ['upf_conv_x3_pack_weights', 'upf_conv_x3_pack_weights_dgrad'],
+                  'stack': ['upf_conv_pack_weights_f32'] * 6 + ['upf_conv_pack_stacked_dgrad']}
+    refs = {}
+    for name, (weights, run) in layers.items():
+        ops.train_caches_clear()
+        del packs[:]
+        cold = run()
+        assert packs == want_packs[name], (name, packs)
+        del packs[:]
+        warm = run()
+        assert packs == [] and same(warm, cold), (name, packs)
+        with torch.no_grad():
+            for w in weights:
+                w.mul_(1.5)                                      # an optimiser step: new versions, new values
+        updated = run()
+        assert packs == want_packs[name], (name, packs)
+        ops.train_caches_clear()
+        refs[name] = run()
+        assert same(updated, refs[name]), name
+        assert not torch.equal(updated[0], cold[0]) and not torch.equal(updated[1], cold[1]), name       # the output, the input's gradient
+    # conv_prepack: one launch for the forms the 16-bit layers asked for (the stride-2 one among them; what was asked survives
+    # train_caches_clear) at the NEW versions
+    prepacked = ('stride1', 'stride2', 'stack')
+    weights = [w for name in prepacked for w in layers[name][0]]
+    with torch.no_grad():
+        for w in weights:
+            w.mul_(1.0)                                          # bump the versions, same values
+    del packs[:]
+    ops.conv_prepack(weights)
+    assert packs == ['upf_conv_pack_weights_f32_multi']
+    for name in prepacked:
+        del packs[:]
+        got = layers[name][1]()
+        assert packs == (['upf_conv_pack_stacked_dgrad'] if name == 'stack' else []), (name, packs)
+        assert same(got, refs[name]), name
+    ops.train_caches_clear()

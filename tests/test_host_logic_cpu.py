@@ -100,41 +100,48 @@ def test_loss_manager_handles_python_zero_terms(stub):
     assert stats['smooth_loss'] == 0.0 and np.isfinite(stats['loss'])
 
 
-def test_training_caches_after_a_capture_keep_what_the_graph_read():
+def test_training_caches_after_a_capture_keep_what_the_graph_read(monkeypatch):
     """Trainer._capture used to clear every training cache — including the zero-bias operand and packs that
     were cache HITS during the capture, whose eager-pool addresses are baked into the graph (use-after-free on the next
     allocation).  Semantics now: entries made during the capture are dropped, entries from before it stay AND are handed to the
     trainer to pin; the zero-bias buffer is never dropped (not by train_caches_clear either)."""
-    import weakref
     from upflow_pytorch_amd import ops
-    saved = (dict(ops._PACK_CACHE), dict(ops._S2D_CACHE), dict(ops._STACK_PACK_CACHE), dict(ops._ZERO_BIAS))
-    try:
-        for c in (ops._PACK_CACHE, ops._S2D_CACHE, ops._STACK_PACK_CACHE, ops._ZERO_BIAS):
-            c.clear()
-        w = torch.zeros(4, 4, 3, 3)
-        old_pack, old_s2d, old_stack, zb = torch.zeros(8), torch.zeros(8), torch.zeros(8), torch.zeros(16)
-        ops._PACK_CACHE[id(w)] = (weakref.ref(w), {('k', 0): old_pack})
-        ops._S2D_CACHE[id(w)] = (('key',), weakref.ref(w), old_s2d)
-        ops._STACK_PACK_CACHE[('ids',)] = (('key',), [weakref.ref(w)], old_stack)
-        ops._ZERO_BIAS['dev'] = zb
-        mark = ops.train_caches_mark()
-        # "during the capture": a new version of w is packed, another parameter appears
-        w2 = torch.zeros(2, 2, 3, 3)
-        new_pack, new_pack2, new_stack = torch.ones(8), torch.ones(8), torch.ones(8)
-        ops._PACK_CACHE[id(w)][1][('k', 1)] = new_pack
-        ops._PACK_CACHE[id(w2)] = (weakref.ref(w2), {('k', 0): new_pack2})
-        ops._STACK_PACK_CACHE[('ids2',)] = (('key',), [weakref.ref(w2)], new_stack)
-        keep = ops.train_caches_after_capture(mark)
-        assert {id(t) for t in keep} == {id(old_pack), id(old_s2d), id(old_stack), id(zb)}
-        assert list(ops._PACK_CACHE[id(w)][1].values()) == [old_pack] and id(w2) not in ops._PACK_CACHE
-        assert list(ops._STACK_PACK_CACHE) == [('ids',)] and id(w) in ops._S2D_CACHE
-        ops.train_caches_clear()
-        assert not ops._PACK_CACHE and not ops._S2D_CACHE and not ops._STACK_PACK_CACHE
-        assert ops._ZERO_BIAS['dev'] is zb                                  # never dropped
-    finally:
-        for c, s_ in zip((ops._PACK_CACHE, ops._S2D_CACHE, ops._STACK_PACK_CACHE, ops._ZERO_BIAS), saved):
-            c.clear()
-            c.update(s_)
+    from upflow_pytorch_amd._operand_cache import OperandCache
+    cache, zb = OperandCache(), torch.zeros(16)
+    monkeypatch.setattr(ops, '_OPERANDS', cache)
+    monkeypatch.setattr(ops, '_ZERO_BIAS', {'dev': zb})
+    dt = torch.bfloat16
+    w, frozen, frozen2 = torch.zeros(4, 4, 3, 3), torch.zeros(4, 4, 3, 3), torch.zeros(4, 4, 3, 3)
+    old_pack, old_s2d, old_stack, old_pool = torch.zeros(8), torch.zeros(8), [torch.zeros(8)], torch.zeros(8)
+    cache.put((w,), ('pack', dt, 0), old_pack)
+    cache.put((frozen,), ('pack', dt, 2), old_s2d)
+    cache.put((frozen, frozen2), ('stacks', ((0, 4, 1),), dt), old_stack, alloc=old_pool)
+    mark = ops.train_caches_mark()
+    # "during the capture": the optimiser moves w and its new version is packed (replacing the old pack), another parameter and
+    # another stack appear, the operands of the frozen parameters are hit
+    w.add_(0)
+    w2 = torch.zeros(2, 2, 3, 3)
+    new_pack, new_pack2, new_stack = torch.ones(8), torch.ones(8), torch.ones(8)
+    assert cache.get((w,), ('pack', dt, 0)) is None
+    cache.put((w,), ('pack', dt, 0), new_pack)
+    cache.put((w2,), ('pack', dt, 0), new_pack2)
+    cache.put((w2, frozen), ('stack', 0, 4, dt), new_stack)
+    assert cache.get((frozen,), ('pack', dt, 2)) is old_s2d and cache.get((frozen, frozen2), ('stacks', ((0, 4, 1),), dt)) is old_stack
+    assert cache.get((w,), ('pack', dt, 0)) is new_pack
+    keep = ops.train_caches_after_capture(mark)
+    # everything from before the mark is handed to the trainer — the replaced pack too —, by identity, and nothing else
+    assert sorted(id(t) for t in keep) == sorted(id(t) for t in (old_pack, old_s2d, old_pool, zb))
+    # nothing made during the capture can be found
+    assert cache.get((w,), ('pack', dt, 0)) is None and cache.get((w2,), ('pack', dt, 0)) is None
+    assert cache.get((w2, frozen), ('stack', 0, 4, dt)) is None
+    # what was only hit stays, the very objects
+    assert cache.get((frozen,), ('pack', dt, 2)) is old_s2d and cache.get((frozen, frozen2), ('stacks', ((0, 4, 1),), dt)) is old_stack
+    assert len(cache) == 2 and sorted(id(t) for t in ops._train_cache_tensors()) == sorted(id(t) for t in (old_s2d, old_pool, zb))
+    assert cache.forms_seen(w) == {('pack', dt, 0)} and cache.forms_seen(w2) == {('pack', dt, 0)} and cache.forms_seen(frozen) == {('pack', dt, 2)}
+    ops.train_caches_clear()
+    assert len(cache) == 0 and cache.tensors() == [] and cache.get((frozen,), ('pack', dt, 2)) is None
+    assert ops._ZERO_BIAS['dev'] is zb and ops._train_cache_tensors() == [zb]        # never dropped
+    assert ops.conv_pack_cache_clear is ops.train_caches_clear
 
 
 def test_fused_optimizer_steps_advance_parameter_versions():

@@ -4,12 +4,12 @@ Each operator = one HIP launch on the current torch stream.  Flows, sampling pos
 are fp32 whatever the feature dtype.  No CPU path: non-GPU tensors raise.
 """
 import os
-import weakref
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
+from ._operand_cache import OperandCache
 from ._lib import MASK_NONE, MASK_LITERAL, MASK_ROBUST, UpflowHipError  # noqa: F401
 
 _MASKS = {None: MASK_NONE, 'none': MASK_NONE, 'literal': MASK_LITERAL, 'robust': MASK_ROBUST,
@@ -1377,35 +1377,19 @@ def smooth_edge1(img, pred):
 # ------------------------------------------------------------------------------------------------
 # convolution under autograd on the matrix cores (training; csrc/conv3x3.hip + csrc/conv_wgrad.hip)
 # ------------------------------------------------------------------------------------------------
-_PACK_CACHE = {}
+_OPERANDS = OperandCache()      # every packed weight operand of the training path; forms: ('pack', dtype, mode), ('x3', dgrad),
+#                                 ('stack', channel, width, dtype), ('stacks', slices, dtype)
 
 
 def conv_pack_from_master(weight32, dtype, dgrad=False):
-    """fp32 master weights [Cout,Cin,k,k] -> the MFMA kernel's packed 16-bit operand, for the forward convolution or
-    (dgrad) for its data gradient (flipped, transposed kernel).  Cached per parameter VERSION: the decoder's layers are
-    shared by the five pyramid levels, so a training step packs every layer once per direction instead of ten times
-    (the optimiser's in-place update bumps the version; `.data` surgery needs conv_pack_cache_clear())."""
-    key = (weight32.data_ptr(), weight32._version, dtype, bool(dgrad))
-    slot = _PACK_CACHE.get(id(weight32))
-    if slot is not None and slot[0]() is not weight32:          # the id was recycled by another tensor: not our entry
-        slot = None
-    if slot is not None and key in slot[1]:
-        return slot[1][key]
-    _pack_wanted(weight32, dtype, 1 if dgrad else 0)
-    packed = _conv_pack_from_master(weight32, dtype, dgrad)
-    if slot is None:
-        if len(_PACK_CACHE) > 4096:
-            _PACK_CACHE.clear()
-        slot = _PACK_CACHE[id(weight32)] = (weakref.ref(weight32), {})
-    for k in [k for k in slot[1] if k[1] != weight32._version or k[0] != weight32.data_ptr()]:
-        del slot[1][k]
-    slot[1][key] = packed
-    return packed
-
-
-def conv_pack_cache_clear():
-    _PACK_CACHE.clear()
-    _X3_TRAIN_CACHE.clear()
+    """fp32 master weights [Cout,Cin,k,k] -> the MFMA kernel's packed 16-bit operand, for the forward convolution, (dgrad) for
+    its data gradient (flipped, transposed kernel) or (dgrad = 2) for the data gradient of the space-to-depth form of a stride-2
+    layer.  Cached per parameter VERSION (_OPERANDS): the decoder's layers are shared by the five pyramid levels, so a training
+    step packs every layer once per direction instead of ten times (the optimiser's in-place update bumps the version, `.data`
+    surgery moves the storage: both miss; train_caches_clear() drops everything)."""
+    form = ('pack', dtype, int(dgrad))
+    hit = _OPERANDS.get((weight32,), form)
+    return hit if hit is not None else _OPERANDS.put((weight32,), form, _conv_pack_from_master(weight32, dtype, dgrad))
 
 
 # The packed 16-bit weight copies (here and in model/pwc_modules._PackedConv*) and runtime.GraphedInference's staleness check are
@@ -1431,136 +1415,81 @@ def register_version_hook(optimizer):
     return handle
 
 
+def _carve(sizes, dtype, device):
+    """-> (pool, views): ONE allocation and a 16-byte-aligned view of >= n elements of a 16-bit `dtype` for every n in sizes."""
+    sizes = [(n + 7) // 8 * 8 for n in sizes]
+    pool = torch.empty((sum(sizes),), dtype=dtype, device=device)
+    return pool, list(pool.split(sizes))
+
+
+def _packed_elems(Cout, Cin, k, mode):
+    """Elements of the 16-bit operand conv_pack_from_master(w [Cout,Cin,k,k], dtype, mode) makes."""
+    if mode == 2:
+        return _lib.lib().upf_conv_packed_bytes(Cout, 4 * Cin, 3) // 2
+    return _lib.lib().upf_conv_packed_bytes(Cout if mode else Cin, Cin if mode else Cout, k) // 2
+
+
 # ---- every layer's operands in one launch ---------------------------------------------------------------------------------
 # A training step re-packs ~60 operands (forward / data-gradient form of every layer) after the optimiser has changed the
 # fp32 master weights: 60 launches of 3-5 us.  The per-layer packers above REMEMBER what was asked of each parameter
-# (_PACK_WANTED); conv_prepack(weights) — called by shared_conv_grads at the start of a forward — then makes all of them for
-# the current parameter versions in ONE launch (upf_conv_pack_weights_f32_multi) and the per-layer calls find them cached.
-_PACK_WANTED = {}
-
-
-def _pack_wanted(weight32, dtype, mode):
-    slot = _PACK_WANTED.get(id(weight32))
-    if slot is None or slot[0]() is not weight32:
-        if len(_PACK_WANTED) > 4096:
-            _PACK_WANTED.clear()
-        slot = _PACK_WANTED[id(weight32)] = (weakref.ref(weight32), set())
-    slot[1].add((dtype, mode))
-
-
+# (_OPERANDS.forms_seen); conv_prepack(weights) — called by shared_conv_grads at the start of a forward — then makes all of them
+# for the current parameter versions in ONE launch (upf_conv_pack_weights_f32_multi) and the per-layer calls find them cached.
 def conv_prepack(weights):
     """Pack, in one launch, every operand form the per-layer packers have been asked for so far (forward, data gradient,
-    space-to-depth data gradient) of the given fp32 master weights at their CURRENT versions; fills the same caches."""
+    space-to-depth data gradient) of the given fp32 master weights at their CURRENT versions; fills the same cache."""
     import ctypes
-    jobs = []
-    for w in weights:
-        slot = _PACK_WANTED.get(id(w))
-        if slot is None or slot[0]() is not w or not w.is_cuda or w.dtype != torch.float32 or not w.is_contiguous():
-            continue
-        Cout, Cin, k, _ = w.shape
-        for (dtype, mode) in slot[1]:
-            if mode == 2:
-                hit = _S2D_CACHE.get(id(w))
-                if hit is not None and hit[0] == (w._version, w.data_ptr(), dtype) and hit[1]() is w:
-                    continue
-                nbytes = _lib.lib().upf_conv_packed_bytes(Cout, 4 * Cin, 3)
-            else:
-                cs = _PACK_CACHE.get(id(w))
-                if cs is not None and cs[0]() is w and (w.data_ptr(), w._version, dtype, bool(mode)) in cs[1]:
-                    continue
-                nbytes = _lib.lib().upf_conv_packed_bytes(Cout if mode else Cin, Cin if mode else Cout, k)
-            jobs.append((w, dtype, mode, nbytes))
     by_dev = {}
-    for j in jobs:
-        by_dev.setdefault((j[0].device, j[1]), []).append(j)
+    for w in weights:
+        if not w.is_cuda or w.dtype != torch.float32 or not w.is_contiguous():
+            continue
+        for form in _OPERANDS.forms_seen(w):
+            if form[0] == 'pack' and _OPERANDS.get((w,), form) is None:
+                by_dev.setdefault((w.device, form[1]), []).append((w, form))
     for (dev, dtype), js in by_dev.items():
         if len(js) < 2:
             continue                                            # (the per-layer packer does a single one just as well)
-        sizes = [(j[3] // 2 + 7) // 8 * 8 for j in js]          # elements, every operand 16-byte aligned
-        pool = torch.empty((sum(sizes),), dtype=dtype, device=dev)
-        outs, o = [], 0
-        for n in sizes:
-            outs.append(pool[o:o + n])
-            o += n
+        elems = [_packed_elems(w.shape[0], w.shape[1], w.shape[2], form[2]) for w, form in js]
+        pool, outs = _carve(elems, dtype, dev)
         n = len(js)
-        wp = (ctypes.c_void_p * n)(*[j[0].data_ptr() for j in js])
+        wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w, _ in js])
         op = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-        ci = (ctypes.c_int * n)(*[j[0].shape[1] for j in js])
-        co = (ctypes.c_int * n)(*[j[0].shape[0] for j in js])
-        ks = (ctypes.c_int * n)(*[j[0].shape[2] for j in js])
-        dg = (ctypes.c_int * n)(*[j[2] for j in js])
+        ci = (ctypes.c_int * n)(*[w.shape[1] for w, _ in js])
+        co = (ctypes.c_int * n)(*[w.shape[0] for w, _ in js])
+        ks = (ctypes.c_int * n)(*[w.shape[2] for w, _ in js])
+        dg = (ctypes.c_int * n)(*[form[2] for _, form in js])
         with torch.cuda.device(dev):
             _lib.call('upf_conv_pack_weights_f32_multi', wp, op, ci, co, ks, dg, n, _lib.dtype_code(pool), _lib.stream_ptr(dev))
-        for (w, dtype, mode, nbytes), t in zip(js, outs):
-            packed = t[:nbytes // 2]
-            if mode == 2:
-                _S2D_CACHE[id(w)] = ((w._version, w.data_ptr(), dtype), weakref.ref(w), packed)
-            else:
-                cs = _PACK_CACHE.get(id(w))
-                if cs is None or cs[0]() is not w:
-                    cs = _PACK_CACHE[id(w)] = (weakref.ref(w), {})
-                for k_ in [k_ for k_ in cs[1] if k_[1] != w._version or k_[0] != w.data_ptr()]:
-                    del cs[1][k_]
-                cs[1][(w.data_ptr(), w._version, dtype, bool(mode))] = packed
+        for (w, form), t, ne in zip(js, outs, elems):
+            _OPERANDS.put((w,), form, t[:ne])
 
 
 def _train_cache_tensors():
     """Every device tensor the training-path caches hold right now (packed operands, the zero-bias buffers)."""
-    out = []
-    for slot in _PACK_CACHE.values():
-        out.extend(slot[1].values())
-    out.extend(v[2] for v in _S2D_CACHE.values())
-    out.extend(v[2] for v in _STACK_PACK_CACHE.values())
-    out.extend(v[2] for v in _X3_TRAIN_CACHE.values())
-    out.extend(_ZERO_BIAS.values())
-    return out
+    return _OPERANDS.tensors() + list(_ZERO_BIAS.values())
 
 
 def train_caches_mark():
     """Snapshot taken right BEFORE a hipGraph capture of a training step: the cached tensors that exist — the OBJECTS, held for as
-    long as the mark lives (round 4 kept their id()s only: the per-layer packers delete old-version entries during the capture,
-    CPython readily hands a freed object's id to a new one, and a pack made inside the capture could then pass for a
-    pre-existing one — ADVICE r4)."""
+    long as the mark lives (OperandCache, 3)."""
     return {id(t): t for t in _train_cache_tensors()}
 
 
-def _marked(mark, t):
-    return mark.get(id(t)) is t
-
-
 def train_caches_after_capture(mark):
-    """Called right AFTER a capture attempt (train.Trainer._capture).  Two hazards, two answers:
-      * entries made DURING the capture live in graph-pool memory and their packing kernels were only RECORDED: an eager step
-        that found them would multiply by garbage -> they are dropped from the caches (the captured step re-runs its packing
-        kernels at every replay and does not need the cache);
-      * entries that existed BEFORE the capture and were cache HITS during it (the zero-bias buffer, the packs of frozen /
-        grad-less parameters whose version did not move) have their eager-pool ADDRESSES baked into the graph: dropping the
-        only reference would hand that memory to the next eager allocation and the replays would read it -> they stay in the
-        caches, and the full list of pre-capture tensors is RETURNED so that the trainer keeps them alive as long as its graph
-        (whatever another trainer or a cache eviction does to the dictionaries later).
-    The zero-bias buffers are never dropped."""
-    keep = list(mark.values())
-    for wid in list(_PACK_CACHE):
-        ref, d = _PACK_CACHE[wid]
-        for k in [k for k, t in d.items() if not _marked(mark, t)]:
-            del d[k]
-        if not d:
-            del _PACK_CACHE[wid]
-    for cache in (_S2D_CACHE, _STACK_PACK_CACHE, _X3_TRAIN_CACHE):
-        for k in [k for k, v in cache.items() if not _marked(mark, v[2])]:
-            del cache[k]
-    return keep
+    """Called right AFTER a capture attempt (train.Trainer._capture): the operands made during the capture are dropped from the
+    cache, those from before it stay, and the full list of pre-capture tensors is RETURNED so that the trainer keeps them alive
+    as long as its graph (OperandCache, 4).  The zero-bias buffers are never dropped."""
+    _OPERANDS.keep_only(mark)
+    return list(mark.values())
 
 
 def train_caches_clear():
-    """Drop the caches of packed / derived weights of the training path (per-parameter-version packs, stride-2 data-gradient
-    packs, stacked data-gradient packs) — for `.data` surgery on parameters.  NOT the zero-bias buffer: its address may be
-    baked into a captured training graph; and a live captured trainer holds its own references to what it read
-    (train_caches_after_capture), so clearing here cannot invalidate a graph."""
-    _PACK_CACHE.clear()
-    _S2D_CACHE.clear()
-    _STACK_PACK_CACHE.clear()
-    _X3_TRAIN_CACHE.clear()
+    """Drop every packed / derived weight operand of the training path.  NOT the zero-bias buffers: their addresses may be baked
+    into a captured training graph, and nothing else holds them; a live captured trainer holds its own references to the operands
+    it read (train_caches_after_capture), so clearing here cannot invalidate a graph."""
+    _OPERANDS.clear()
+
+
+conv_pack_cache_clear = train_caches_clear
 
 
 def _conv_pack_from_master(weight32, dtype, dgrad=False):
@@ -1569,10 +1498,9 @@ def _conv_pack_from_master(weight32, dtype, dgrad=False):
         w = w.float().contiguous()
     Cout, Cin, k, _ = w.shape
     dev = _lib.check_gpu(w)
-    nbytes = _lib.lib().upf_conv_packed_bytes(Cout if dgrad else Cin, Cin if dgrad else Cout, k)
-    packed = torch.empty((nbytes // 2,), dtype=dtype, device=w.device)
+    packed = torch.empty((_packed_elems(Cout, Cin, k, int(dgrad)),), dtype=dtype, device=w.device)
     with torch.cuda.device(dev):
-        _lib.call('upf_conv_pack_weights_f32', _lib.ptr(w), _lib.ptr(packed), Cin, Cout, k, _lib.dtype_code(packed), int(bool(dgrad)), _lib.stream_ptr(dev))
+        _lib.call('upf_conv_pack_weights_f32', _lib.ptr(w), _lib.ptr(packed), Cin, Cout, k, _lib.dtype_code(packed), int(dgrad), _lib.stream_ptr(dev))
     return packed
 
 
@@ -1632,15 +1560,21 @@ def conv_bias_grad_finish(parts, Cout):
     return total
 
 
-def _wgrad_levels(chunk, Cin, Cout):
-    """ctypes array of upf_wgrad_level for the uses [(x, g), ...] (checked: channel slices of the right shapes)."""
-    arr = (_lib.WgradLevel * len(chunk))()
-    for a, (x, g) in zip(arr, chunk):
-        if not (_is_slice(x) and _is_slice(g)) or x.shape[1] != Cin or g.shape[1] != Cout or x.shape[0] != g.shape[0] or x.shape[2:] != g.shape[2:]:
-            raise UpflowHipError('conv_wgrad_multi: x / g must be [B,Cin,H,W] / [B,Cout,H,W] channel slices')
+def _fill_wgrad_levels(pairs):
+    """ctypes array of upf_wgrad_level for the uses [(x, g), ...]; the callers check the shapes."""
+    arr = (_lib.WgradLevel * len(pairs))()
+    for a, (x, g) in zip(arr, pairs):
         a.x, a.x_batch_stride, a.grad_pre, a.g_batch_stride = x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0)
         a.B, a.H, a.W = x.shape[0], x.shape[2], x.shape[3]
     return arr
+
+
+def _wgrad_levels(chunk, Cin, Cout):
+    """The same, checked: x / g channel slices of the right shapes."""
+    for x, g in chunk:
+        if not (_is_slice(x) and _is_slice(g)) or x.shape[1] != Cin or g.shape[1] != Cout or x.shape[0] != g.shape[0] or x.shape[2:] != g.shape[2:]:
+            raise UpflowHipError('conv_wgrad_multi: x / g must be [B,Cin,H,W] / [B,Cout,H,W] channel slices')
+    return _fill_wgrad_levels(chunk)
 
 
 def conv_wgrad_multi(uses, Cin, Cout, k, dilation, bias_parts=None):
@@ -1808,9 +1742,6 @@ def _zero_bias(device, n):
 # upf_conv_wgrad_s2d), and the data gradient the stride-1 data gradient with w4 (packed straight from w,
 # upf_conv_pack_weights_f32(dgrad = 2)), shuffled back (upf_space_to_depth2).  4x the flops of the minimum on layers that hold 2 % of the step's
 # flops — against PyTorch-ROCm's fp32 gradient kernels, their casts and NCHW<->NHWC transposes (1.2 ms of a 13.3 ms step).
-_S2D_CACHE = {}
-
-
 def space_to_depth2(t, inverse=False):
     """xs[n, c*4 + p*2 + q, i, j] = x[n, c, 2i+p, 2j+q] (= F.pixel_unshuffle(x, 2)); inverse: F.pixel_shuffle(xs, 2)."""
     t = t.contiguous()
@@ -1828,10 +1759,7 @@ def conv_wgrad_s2d(xs, g, Cin, Cout):
     """Weight gradient [Cout,Cin,3,3] of a stride-2 3x3 layer from its space-to-depth input xs [B,4*Cin,H/2,W/2] and the
     gradient g [B,Cout,H/2,W/2] entering its pre-activation (upf_conv_wgrad_s2d)."""
     dev = _lib.check_gpu(xs, g)
-    arr = (_lib.WgradLevel * 1)()
-    a = arr[0]
-    a.x, a.x_batch_stride, a.grad_pre, a.g_batch_stride = xs.data_ptr(), xs.stride(0), g.data_ptr(), g.stride(0)
-    a.B, a.H, a.W = xs.shape[0], xs.shape[2], xs.shape[3]
+    arr = _fill_wgrad_levels([(xs, g)])
     nbytes = _lib.lib().upf_conv_wgrad_multi_workspace_bytes(arr, 1, 4 * Cin, Cout, 3, 1)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     gw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=dev)
@@ -1845,27 +1773,6 @@ def _s2d_ok(x, weight, stride, dilation):
     H, W = x.shape[2:]
     return (stride == 2 and k == 3 and dilation == 1 and H % 2 == 0 and W % 2 == 0 and W // 2 >= 8 and x.dtype in (torch.bfloat16, torch.float16)
             and bool(_lib.lib().upf_conv_wgrad_supported(4 * Cin, Cout, H // 2, W // 2, 3, 1, 1, _lib.dtype_code(x))))
-
-
-def _s2d_dgrad_pack(master, dtype):
-    """Packed data-gradient operand of the space-to-depth form of a stride-2 layer (cached per parameter version)."""
-    key = (master._version, master.data_ptr(), dtype)
-    slot = _S2D_CACHE.get(id(master))
-    if slot is not None and slot[0] == key and slot[1]() is master:
-        return slot[2]
-    _pack_wanted(master, dtype, 2)
-    Cout, Cin = master.shape[:2]
-    w = master.detach()
-    if w.dtype != torch.float32 or not w.is_contiguous():
-        w = w.float().contiguous()
-    dev = _lib.check_gpu(w)
-    packed = torch.empty((_lib.lib().upf_conv_packed_bytes(Cout, 4 * Cin, 3) // 2,), dtype=dtype, device=w.device)
-    with torch.cuda.device(dev):
-        _lib.call('upf_conv_pack_weights_f32', _lib.ptr(w), _lib.ptr(packed), Cin, Cout, 3, _lib.dtype_code(packed), 2, _lib.stream_ptr(dev))
-    if len(_S2D_CACHE) > 1024:
-        _S2D_CACHE.clear()
-    _S2D_CACHE[id(master)] = (key, weakref.ref(master), packed)
-    return packed
 
 
 class ConvTrainFunction(Function):
@@ -1915,7 +1822,7 @@ class ConvTrainFunction(Function):
             B, _, H, W = x.shape
             if ctx.needs_input_grad[0]:
                 gxs = torch.empty((B, 4 * Cin, H // 2, W // 2), dtype=x.dtype, device=x.device)
-                conv3x3_forward_raw(g, _s2d_dgrad_pack(master, x.dtype), _zero_bias(x.device, 4 * Cin), gxs, 1, 0.0, 1, 3)
+                conv3x3_forward_raw(g, conv_pack_from_master(master, x.dtype, dgrad=2), _zero_bias(x.device, 4 * Cin), gxs, 1, 0.0, 1, 3)
                 gx = space_to_depth2(gxs, inverse=True)
             if ctx.needs_input_grad[1]:
                 gw = conv_wgrad_s2d(space_to_depth2(x), g, Cin, Cout)
@@ -1953,17 +1860,14 @@ def conv_train(x, weight, bias, dilation=1, slope=0.0, stride=1):
 
 
 # ---- the fp32 training step on the matrix cores: split-precision convolutions under autograd (csrc/conv_x3_bwd.hip) -------------
-_X3_TRAIN_CACHE = {}         # (id(master), dgrad) -> ((version, data_ptr), weakref, packed operand)
-
-
 def conv_x3_pack_from_master(weight32, dgrad=False):
     """fp32 master weights [Cout,Cin,k,k] -> the split-precision kernel's packed fp16 hi / lo operand, for the forward convolution
     or (dgrad) for the data gradient of a stride-1 layer (flipped, transposed kernel).  Cached per parameter VERSION like
-    conv_pack_from_master; cleared by conv_pack_cache_clear / train_caches_clear."""
-    key = (weight32._version, weight32.data_ptr())
-    slot = _X3_TRAIN_CACHE.get((id(weight32), bool(dgrad)))
-    if slot is not None and slot[0] == key and slot[1]() is weight32:
-        return slot[2]
+    conv_pack_from_master, in the same cache (_OPERANDS; train_caches_clear)."""
+    form = ('x3', bool(dgrad))
+    hit = _OPERANDS.get((weight32,), form)
+    if hit is not None:
+        return hit
     w = weight32.detach()
     if w.dtype != torch.float32 or not w.is_contiguous():
         raise UpflowHipError('conv_x3_train: contiguous fp32 master weights expected')
@@ -1976,10 +1880,7 @@ def conv_x3_pack_from_master(weight32, dgrad=False):
     with torch.cuda.device(dev):
         _lib.call('upf_conv_x3_pack_weights_dgrad' if dgrad else 'upf_conv_x3_pack_weights', _lib.ptr(w), _lib.ptr(packed), Cin, Cout, k,
                   _lib.stream_ptr(dev))
-    if len(_X3_TRAIN_CACHE) > 4096:
-        _X3_TRAIN_CACHE.clear()
-    _X3_TRAIN_CACHE[(id(weight32), bool(dgrad))] = (key, weakref.ref(weight32), packed)
-    return packed
+    return _OPERANDS.put((weight32,), form, packed)
 
 
 def act_grad_x3(gy, y=None, slope=0.0, want_bias=False):
@@ -2029,16 +1930,14 @@ def conv_x3_wgrad(uses, Cin, Cout, k, dilation=1, stride=1, want_bias=False):
         raise UpflowHipError('conv_x3_wgrad: 1..6 uses')
     dev = uses[0][0].device
     d = int(dilation) if k == 3 else 1
-    arr = (_lib.WgradLevel * len(uses))()
-    for a, (x, g, slot, part) in zip(arr, uses):
+    for x, g, slot, part in uses:
         B, _, H, W = x.shape
         Ho, Wo = conv3x3_out_hw(H, W, stride)
         if (not _is_slice(x) or not _is_slice(g) or x.shape[1] != Cin or tuple(g.shape) != (B, Cout, Ho, Wo)
                 or x.dtype != torch.float32 or g.dtype != torch.float32):
             raise UpflowHipError('conv_x3_wgrad: x [B,%d,H,W] and g [B,%d,Ho,Wo] fp32 channel slices expected' % (Cin, Cout))
         _lib.check_gpu(x, g, slot, part, contiguous=False)
-        a.x, a.x_batch_stride, a.grad_pre, a.g_batch_stride = x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0)
-        a.B, a.H, a.W = B, H, W
+    arr = _fill_wgrad_levels([u[:2] for u in uses])
     nbytes = ctypes.c_longlong(0)
     _lib.call('upf_conv_x3_wgrad_workspace_bytes', arr, len(uses), Cin, Cout, k, d, int(stride), ctypes.byref(nbytes))
     ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
@@ -2103,26 +2002,19 @@ def conv_x3_train(x, weight, bias, dilation=1, slope=0.0, stride=1):
 
 
 # ---- a whole dense stack (conv1..conv5 + conv_last) under autograd, in ONE buffer ---------------------------------------
-_STACK_PACK_CACHE = {}
-
-
 def _stacked_dgrad_pack(masters, lo, hi_of, lo_k, f_k, dtype):
     """Packed data-gradient operand for the buffer channels [lo_k, lo_k + f_k) with respect to the pre-activation gradients
     of the layers `masters` (ordered like the gradient buffer: last layer first): the rows of each layer's kernel that
     read those channels, stacked along the (transposed) input dimension.  Cached per parameter versions."""
-    ids = tuple(id(w) for w in masters) + (lo_k, f_k, dtype)
-    key = (tuple(w._version for w in masters), tuple(w.data_ptr() for w in masters))
-    slot = _STACK_PACK_CACHE.get(ids)
-    if slot is not None and slot[0] == key and all(r() is w for r, w in zip(slot[1], masters)):
-        return slot[2]
+    owners, form = tuple(masters), ('stack', lo_k, f_k, dtype)
+    hit = _OPERANDS.get(owners, form)
+    if hit is not None:
+        return hit
     with torch.no_grad():
         parts = [w.detach()[:, lo_k - h:lo_k - h + f_k] for w, h in zip(masters, hi_of)]
         stacked = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts, dim=0)
         packed = _conv_pack_from_master(stacked.float(), dtype, dgrad=True)
-    if len(_STACK_PACK_CACHE) > 1024:
-        _STACK_PACK_CACHE.clear()
-    _STACK_PACK_CACHE[ids] = (key, [weakref.ref(w) for w in masters], packed)
-    return packed
+    return _OPERANDS.put(owners, form, packed)
 
 
 def _stack_dgrad_packs(masters, hi, slices, dtype):
@@ -2131,25 +2023,17 @@ def _stack_dgrad_packs(masters, hi, slices, dtype):
     channel, width, number of consumers = a prefix of masters)].  -> one packed operand per slice, bit-identical to
     _stacked_dgrad_pack's.  Cached per parameter versions (the same operands serve every pyramid level of a step)."""
     import ctypes
-    ids = tuple(id(w) for w in masters) + tuple(slices) + (dtype,)
-    key = (tuple(w._version for w in masters), tuple(w.data_ptr() for w in masters))
-    slot = _STACK_PACK_CACHE.get(ids)
-    if slot is not None and slot[0] == key and all(r() is w for r, w in zip(slot[1], masters)):
-        return slot[3]
+    owners, form = tuple(masters), ('stacks', tuple(slices), dtype)
+    hit = _OPERANDS.get(owners, form)
+    if hit is not None:
+        return hit
     dev = _lib.check_gpu(*masters)
     nl, ns = len(masters), len(slices)
     for w in masters:
         if w.dtype != torch.float32 or not w.is_contiguous() or w.shape[2:] != (3, 3):
             raise UpflowHipError('dense stack: contiguous fp32 3x3 master kernels expected')
-    sizes = []
-    for (c0, width, npos) in slices:
-        nbytes = _lib.lib().upf_conv_packed_bytes(sum(w.shape[0] for w in masters[:npos]), width, 3)
-        sizes.append((nbytes // 2 + 7) // 8 * 8)
-    pool = torch.empty((sum(sizes),), dtype=dtype, device=masters[0].device)
-    outs, o = [], 0
-    for n in sizes:
-        outs.append(pool[o:o + n])
-        o += n
+    pool, outs = _carve([_lib.lib().upf_conv_packed_bytes(sum(w.shape[0] for w in masters[:npos]), width, 3) // 2 for (c0, width, npos) in slices],
+                        dtype, masters[0].device)
     wp = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in masters])
     ci = (ctypes.c_int * nl)(*[w.shape[1] for w in masters])
     co = (ctypes.c_int * nl)(*[w.shape[0] for w in masters])
@@ -2160,10 +2044,7 @@ def _stack_dgrad_packs(masters, hi, slices, dtype):
     sn = (ctypes.c_int * ns)(*[int(c[2]) for c in slices])
     with torch.cuda.device(dev):
         _lib.call('upf_conv_pack_stacked_dgrad', wp, ci, co, hh, nl, op, sc, sw, sn, ns, _lib.dtype_code(pool), _lib.stream_ptr(dev))
-    if len(_STACK_PACK_CACHE) > 1024:
-        _STACK_PACK_CACHE.clear()
-    _STACK_PACK_CACHE[ids] = (key, [weakref.ref(w) for w in masters], pool, outs)     # (slot [2]: the ONE allocation, train_caches_*)
-    return outs
+    return _OPERANDS.put(owners, form, outs, alloc=pool)
 
 
 class DenseStackTrainFunction(Function):

@@ -156,11 +156,9 @@ class Trainer():
                     torch.cuda.graph(g, capture_error_mode='thread_local' if (self.distributed or (dist.is_available() and dist.is_initialized())) else 'global'):
                 self._static_stats = self._step_body(self._static)
         finally:
-            # packed-weight cache entries made DURING the capture point into graph-pool memory whose packing kernels were
-            # only RECORDED: an eager step that found them would multiply by garbage -> dropped.  Entries that
-            # existed BEFORE it and were cache hits inside it (the zero-bias operand of the data-gradient convolutions, packs
-            # of frozen parameters) and the loss module's constants have their eager-pool addresses baked into the graph:
-            # they stay cached AND are pinned here for the graph's lifetime (dropping them was a use-after-free).
+            # what the capture made is dropped from the operand cache; what it only READ — operands from before it, the zero-bias
+            # buffer, the loss module's constants — has its eager-pool address baked into the graph and is pinned here for the
+            # graph's lifetime (_operand_cache.OperandCache, 4)
             # (+ the packed operands of the inference-style holders, pwc_modules._PackedConv*: forwards under no_grad inside the step
             #  read them, and a holder re-packs — frees — its tensor when its parameter's version moves; round 4)
             from .model.pwc_modules import packed_operands
