@@ -455,7 +455,13 @@ int upf_conv_wgrad_multi_bias(const upf_wgrad_level* levels, int nlevels, float*
  *   weight gradient: upf_conv_wgrad_s2d — levels hold xs ([B, 4*Cin, H/2, W/2]) and grad_pre; grad_w is [Cout, Cin, 3, 3]
  *                    (workspace: upf_conv_wgrad_multi_workspace_bytes with Cin := 4*Cin)
  *   data gradient:   upf_conv_pack_weights_f32(w, ..., dgrad = 2) (upf_conv_packed_bytes(Cout, 4*Cin, 3) bytes), then
- *                    upf_conv_forward(grad_pre, ..., Cin := Cout, Cout := 4*Cin) and upf_space_to_depth2(inverse = 1). */
+ *                    upf_conv_forward(grad_pre, ..., Cin := Cout, Cout := 4*Cin) and upf_space_to_depth2(inverse = 1).
+ *                    Exact on finite operands (tests/test_hip_conv_exact.py), but the 27 structural zeros of the packed kernel
+ *                    are multiplied like any weight: a NaN / inf element of grad_pre makes its whole 3x3 neighbourhood of xs
+ *                    pixels — a 6x6 block of x pixels — NaN where the layer's footprint is 3x3 (0 * NaN = NaN).  A caller that
+ *                    needs non-finite gradients confined to the layer's footprint takes the TRANSPOSED form instead, as the
+ *                    Python training path does (ops.ConvTrainFunction): grad_pre copied to the even pixels of a zero
+ *                    [B, Cout, H, W] tensor, then the stride-1 data gradient (dgrad = 1) — the same flops, the zeros are data. */
 int upf_space_to_depth2(const void* src, void* dst, int B, int C /* of x */, int H, int W /* of x, even */, int inverse, int dtype, void* stream);
 int upf_conv_wgrad_s2d(const upf_wgrad_level* levels, int nlevels, float* grad_w, void* workspace, int Cin, int Cout, int dtype, void* stream);
 /* dst = (src + add) * (y > 0 ? 1 : slope) over channel-sliced [B, C, HW] tensors (add, y optional; dst may be src):

@@ -361,9 +361,11 @@ def test_shared_conv_grads_defers_to_one_contraction():
 @pytest.mark.parametrize('shape', [(2, 16, 32, 64), (1, 3, 6, 20), (2, 5, 12, 26), (1, 32, 64, 208)])
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 def test_space_to_depth_and_stride2_gradients(shape, dtype):
-    """upf_space_to_depth2 == F.pixel_unshuffle / F.pixel_shuffle (bit copies), and the stride-2 layer's gradients through its
-    space-to-depth form (upf_conv_wgrad_s2d, upf_conv_pack_weights_f32(dgrad = 2)) vs fp32 autograd of the strided convolution
-    on the same rounded operands (model/pwc_modules.py:95, model/upflow.py:53-55)."""
+    """upf_space_to_depth2 == F.pixel_unshuffle / F.pixel_shuffle (bit copies), and the stride-2 layer's gradients through the
+    stride-1 kernels (weight gradient: upf_conv_wgrad_s2d on the space-to-depth input; data gradient: the transposed form of
+    ops.ConvTrainFunction) vs fp32 autograd of the strided convolution on the same rounded operands (model/pwc_modules.py:95,
+    model/upflow.py:53-55).  The C ABI's upf_conv_pack_weights_f32(dgrad = 2) data gradient has its own test in
+    tests/test_hip_conv_exact.py (test_space_to_depth_data_gradient_of_the_c_abi)."""
     from upflow_pytorch_amd import ops
     B, C, H, W = shape
     g = torch.Generator().manual_seed(sum(shape))

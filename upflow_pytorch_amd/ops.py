@@ -1384,7 +1384,8 @@ _OPERANDS = OperandCache()      # every packed weight operand of the training pa
 def conv_pack_from_master(weight32, dtype, dgrad=False):
     """fp32 master weights [Cout,Cin,k,k] -> the MFMA kernel's packed 16-bit operand, for the forward convolution, (dgrad) for
     its data gradient (flipped, transposed kernel) or (dgrad = 2) for the data gradient of the space-to-depth form of a stride-2
-    layer.  Cached per parameter VERSION (_OPERANDS): the decoder's layers are shared by the five pyramid levels, so a training
+    layer (a C-ABI form conv_train no longer takes: its structural zero weights spread a non-finite gradient element over a 6x6
+    block, include/upflow_hip.h).  Cached per parameter VERSION (_OPERANDS): the decoder's layers are shared by the five pyramid levels, so a training
     step packs every layer once per direction instead of ten times (the optimiser's in-place update bumps the version, `.data`
     surgery moves the storage: both miss; train_caches_clear() drops everything)."""
     form = ('pack', dtype, int(dgrad))
@@ -1435,8 +1436,8 @@ def _packed_elems(Cout, Cin, k, mode):
 # (_OPERANDS.forms_seen); conv_prepack(weights) — called by shared_conv_grads at the start of a forward — then makes all of them
 # for the current parameter versions in ONE launch (upf_conv_pack_weights_f32_multi) and the per-layer calls find them cached.
 def conv_prepack(weights):
-    """Pack, in one launch, every operand form the per-layer packers have been asked for so far (forward, data gradient,
-    space-to-depth data gradient) of the given fp32 master weights at their CURRENT versions; fills the same cache."""
+    """Pack, in one launch, every operand form the per-layer packers have been asked for so far (forward, data gradient;
+    the space-to-depth data-gradient form too, if a caller asked for it) of the given fp32 master weights at their CURRENT versions; fills the same cache."""
     import ctypes
     by_dev = {}
     for w in weights:
@@ -1739,9 +1740,11 @@ def _zero_bias(device, n):
 # space-to-depth input xs[(c, p, q), i, j] = x[c, 2i+p, 2j+q] (F.pixel_unshuffle): a STRIDE-1 3x3 convolution of xs whose
 # kernel w4[co, (ci,p,q), a, b] is w[co, ci, ky, kx] at (p, a) = _S2D(ky), (q, b) = _S2D(kx) and zero elsewhere.  So the
 # weight gradient is the stride-1 weight gradient w.r.t. (xs, g) gathered at those positions (inside the split-K reduction,
-# upf_conv_wgrad_s2d), and the data gradient the stride-1 data gradient with w4 (packed straight from w,
-# upf_conv_pack_weights_f32(dgrad = 2)), shuffled back (upf_space_to_depth2).  4x the flops of the minimum on layers that hold 2 % of the step's
-# flops — against PyTorch-ROCm's fp32 gradient kernels, their casts and NCHW<->NHWC transposes (1.2 ms of a 13.3 ms step).
+# upf_conv_wgrad_s2d).  The data gradient is the TRANSPOSED form: the stride-1 data gradient (flipped, transposed w) of grad_pre spread
+# over the even pixels of a zero grid — the same flops as the stride-1 data gradient with w4 (upf_conv_pack_weights_f32(dgrad = 2),
+# shuffled back by upf_space_to_depth2), which rounds 1-6 used, but its zeros are DATA: w4's structural zero WEIGHTS turned one
+# non-finite gradient element into a 6x6 block of NaN where the layer's footprint is 3x3.  4x the flops of the minimum on layers that
+# hold 2 % of the step's flops — against PyTorch-ROCm's fp32 gradient kernels, their casts and NCHW<->NHWC transposes.
 def space_to_depth2(t, inverse=False):
     """xs[n, c*4 + p*2 + q, i, j] = x[n, c, 2i+p, 2j+q] (= F.pixel_unshuffle(x, 2)); inverse: F.pixel_shuffle(xs, 2)."""
     t = t.contiguous()
@@ -1780,7 +1783,9 @@ class ConvTrainFunction(Function):
     fp32 master weights / bias and fp32 parameter gradients.  Forward on the MFMA kernel of csrc/conv3x3.hip; backward:
     the data gradient of a stride-1 layer is the same kernel on the flipped, transposed weights, the weight gradient is
     csrc/conv_wgrad.hip (stride 1, W >= 8), the LeakyReLU gradient and the first stage of the bias gradient one launch
-    (upf_act_grad); the remaining cases (stride-2 layers) take PyTorch-ROCm's gradient kernels on fp32 copies.  Inside
+    (upf_act_grad).  A stride-2 layer of even size (_s2d_ok) goes through the same kernels: weight gradient of its space-to-depth
+    input (upf_conv_wgrad_s2d), data gradient in the transposed form (grad_pre on the even pixels of a zero grid, then the
+    stride-1 data gradient); only what is left (stride-2 layers of odd size) takes PyTorch-ROCm's gradient kernels on fp32 copies.  Inside
     `shared_conv_grads` the parameter gradients are deferred to the parameter's sink (one contraction over all uses).
     Replaces nn.Conv2d + nn.LeakyReLU (model/pwc_modules.py:10-49) in training."""
 
@@ -1817,13 +1822,15 @@ class ConvTrainFunction(Function):
             g, part = act_grad(gy, y, slope, want_bias=want_b)
         gx = gw = gb = None
         if _s2d_ok(x, weight, stride, dilation):
-            # stride-2 layer as a stride-1 convolution of the space-to-depth input (see _s2d_ok): both gradients on the
+            # stride-2 layer through the stride-1 gradient kernels (see _s2d_ok): both gradients on the
             # matrix-core kernels instead of PyTorch-ROCm's fp32 kernels + casts + layout transposes
             B, _, H, W = x.shape
             if ctx.needs_input_grad[0]:
-                gxs = torch.empty((B, 4 * Cin, H // 2, W // 2), dtype=x.dtype, device=x.device)
-                conv3x3_forward_raw(g, conv_pack_from_master(master, x.dtype, dgrad=2), _zero_bias(x.device, 4 * Cin), gxs, 1, 0.0, 1, 3)
-                gx = space_to_depth2(gxs, inverse=True)
+                # the transposed form (see above): zeros as data, not as weights (tests/test_hip_conv_exact.py, non-finite operands)
+                up = torch.zeros((B, Cout, H, W), dtype=x.dtype, device=x.device)
+                up[:, :, ::2, ::2] = g
+                gx = torch.empty_like(x)
+                conv3x3_forward_raw(up, conv_pack_from_master(master, x.dtype, dgrad=True), _zero_bias(x.device, Cin), gx, 1, 0.0, 1, 3)
             if ctx.needs_input_grad[1]:
                 gw = conv_wgrad_s2d(space_to_depth2(x), g, Cin, Cout)
             if want_b:
