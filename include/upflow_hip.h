@@ -615,6 +615,53 @@ int upf_smooth_edge1_forward(const float* img, const float* pred, float* partial
 int upf_smooth_edge1_backward(const float* img, const float* pred, const float* grad_up, float* grad_pred,
                               int B, int Ci, int Cp, int H, int W, void* stream);
 
+/* ---- non-default loss variants (csrc/loss_variants.hip); fp32 contiguous NCHW, deterministic, no host synchronisation ---- */
+
+/* second-order edge-aware smoothness, network_tools.edge_aware_smoothness_order2 (model/upflow.py:220-243):
+ *   xx(i,j) = (p(i,j) - p(i+1,j)) - (p(i+1,j) - p(i+2,j)),  wx(i,j) = exp(-mean_c |img(i,j) - img(i+2,j)|),  i < H-2; columns likewise;
+ *   partials[k] = { sum |xx| * wx, sum |yy| * wy }  (upf_loss_partials(B*H*W) pairs);
+ *   loss = sum_x / (B*Cp*(H-2)*W) + sum_y / (B*Cp*H*(W-2)).  H, W >= 3.
+ * Backward: gradient wrt pred of that loss times the device scalar grad_up[0] (gather over up to three row and three column
+ * terms with coefficients 1, -2, 1; sign(0) = 0).  No gradient wrt img. */
+int upf_smooth_edge2_forward(const float* img, const float* pred, float* partials,
+                             int B, int Ci, int Cp, int H, int W, void* stream);
+int upf_smooth_edge2_backward(const float* img, const float* pred, const float* grad_up, float* grad_pred,
+                              int B, int Ci, int Cp, int H, int W, void* stream);
+
+/* delta smoothness, network_tools.flow_smooth_delta (model/upflow.py:245-263) on BC = B*C planes [H,W]:
+ *   dx = f(i,j+1) - f(i,j), dy = f(i+1,j) - f(i,j); second_order adds dx2, dxdy (horizontal / vertical difference of dx) and
+ *   dydx, dy2 (of dy), each built from the first differences;
+ *   partials[k][0..1] (or [0..5]) = sums of |dx|, |dy| [, |dx2|, |dxdy|, |dydx|, |dy2|]  (upf_loss_partials(BC*H*W) rows);
+ *   loss = sum of the terms' means.  H, W >= 2 (>= 3 with second_order).
+ * Backward: gradient of that loss times the device scalar grad_up[0] (one gather). */
+int upf_smooth_delta_forward(const float* flow, float* partials, int BC, int H, int W, int second_order, void* stream);
+int upf_smooth_delta_backward(const float* flow, const float* grad_up, float* grad_flow, int BC, int H, int W,
+                              int second_order, void* stream);
+
+/* point-wise photometric kinds of network_tools.photo_loss_multi_type (model/upflow.py:273-278, :284-287), the shape of
+ * upf_robust_loss_*:  UPF_LOSS_CHARBONNIER ((x-y)^2 + 1e-6)^q,  UPF_LOSS_L1 |x - y + 1e-6|  (q unused);
+ *   partials[k] = { sum loss * occ, sum occ }  (upf_loss_partials(B*HW) pairs; occ [B,HW] or NULL = 1, summed once per pixel).
+ * Backward: grad_x = coef[0] * occ * d loss / d (x-y), grad_y = -grad_x (either may be NULL); coef is a DEVICE scalar. */
+enum { UPF_LOSS_CHARBONNIER = 0, UPF_LOSS_L1 = 1 };
+int upf_pointwise_loss_forward(const float* x, const float* y, const float* occ, float* partials,
+                               int B, int C, int HW, int kind, float q, void* stream);
+int upf_pointwise_loss_backward(const float* x, const float* y, const float* occ, const float* coef,
+                                float* grad_x, float* grad_y, int B, int C, int HW, int kind, float q, void* stream);
+
+/* weighted SSIM, network_tools.weighted_ssim (model/upflow.py:139-195) with c1 = inf and finite c2 > 0:  x, y [B,C,H,W],
+ * weight [B,1,H,W], 3x3 VALID windows, H, W >= 3.  Forward, one launch, every output optional (NULL):
+ *   map [B,C,H-2,W-2] = clamp((1 - (2 sigma_xy + c2) / (sigma_x + sigma_y + c2)) / 2, 0, 1),  w_avg [B,1,H-2,W-2] = avg_pool(weight),
+ *   partials[k] = { sum map * w_avg, sum w_avg (once per window), sum map }  (upf_loss_partials(B*(H-2)*(W-2)) triples).
+ * Backward, one launch: the upstream gradient of window p, channel c is
+ *   grad_map[p,c] (if given) + coef_w[0] * w_avg(p) (if given) + coef_u[0] (if given)      — coef_w, coef_u DEVICE scalars;
+ * grad_x / grad_y (either may be NULL) gather it through at most nine windows per pixel; the clamp passes the gradient on
+ * [0,1] inclusive.  No gradient wrt weight. */
+int upf_ssim_forward(const float* x, const float* y, const float* weight, float* map, float* w_avg, float* partials,
+                     int B, int C, int H, int W, float c2, float weight_epsilon, void* stream);
+int upf_ssim_backward(const float* x, const float* y, const float* weight, const float* grad_map,
+                      const float* coef_w, const float* coef_u, float* grad_x, float* grad_y,
+                      int B, int C, int H, int W, float c2, float weight_epsilon, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

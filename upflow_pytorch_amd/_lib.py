@@ -96,6 +96,14 @@ SIGNATURES = {
     'upf_msd_upup_backward': [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp],
     'upf_smooth_edge1_forward': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     'upf_smooth_edge1_backward': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    'upf_smooth_edge2_forward': [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    'upf_smooth_edge2_backward': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    'upf_smooth_delta_forward': [_vp, _vp, _i, _i, _i, _i, _vp],
+    'upf_smooth_delta_backward': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    'upf_pointwise_loss_forward': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    'upf_pointwise_loss_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    'upf_ssim_forward': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp],
+    'upf_ssim_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp],
     'upf_div_selftest': [_i, _vp, _vp],
     'upf_occ_check': [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp],
 }

@@ -173,9 +173,18 @@ class network_tools():
         """model/upflow.py:197-216 — one fused reduction launch (csrc/loss.hip: upf_smooth_edge1_*)."""
         return ops.smooth_edge1(img, pred)
 
+    # The non-default variants below run natively (csrc/loss_variants.hip, one launch forward and one backward each) when every
+    # tensor is float32 on the GPU and at least as large as the stencil; otherwise, or with native=False (`net._no_native_loss_variants
+    # = True` makes _losses pass that), they are the torch spelling of the reference, kept as the private _*_torch classmethods.
     @classmethod
-    def edge_aware_smoothness_order2(cls, img, pred):
-        """model/upflow.py:218-243."""
+    def edge_aware_smoothness_order2(cls, img, pred, native=True):
+        """model/upflow.py:220-243."""
+        if native and ops.loss_variant_operands_ok(img, pred, min_hw=3):
+            return ops.smooth_edge2(img.contiguous(), pred.contiguous())
+        return cls._edge_aware_smoothness_order2_torch(img, pred)
+
+    @classmethod
+    def _edge_aware_smoothness_order2_torch(cls, img, pred):
         def dx(t, s=1):
             return t[:, :, :-s, :] - t[:, :, s:, :]
 
@@ -186,12 +195,25 @@ class network_tools():
         return (dx(dx(pred)).abs() * wx).mean() + (dy(dy(pred)).abs() * wy).mean()
 
     @classmethod
-    def flow_smooth_delta(cls, flow, if_second_order=False):
-        return loss_functions.flow_smooth_delta(flow, if_second_order)
+    def flow_smooth_delta(cls, flow, if_second_order=False, native=True):
+        return loss_functions.flow_smooth_delta(flow, if_second_order, native=native)
 
     @classmethod
-    def weighted_ssim(cls, x, y, weight, c1=float('inf'), c2=9e-6, weight_epsilon=0.01):
-        """model/upflow.py:139-195."""
+    def _ssim_native_ok(cls, x, y, weight, c1, c2, native):
+        return (native and c1 == float('inf') and 0.0 < c2 < float('inf') and not weight.requires_grad
+                and x.shape == y.shape and ops.loss_variant_operands_ok(x, y, weight, min_hw=3))
+
+    @classmethod
+    def weighted_ssim(cls, x, y, weight, c1=float('inf'), c2=9e-6, weight_epsilon=0.01, native=True):
+        """model/upflow.py:139-195 -> (loss map, pooled weight); natively for c1 = inf and a weight that needs no gradient."""
+        if c1 == float('inf') and c2 == float('inf'):
+            raise ValueError('Both c1 and c2 are infinite, SSIM loss is zero. This is likely unintended.')
+        if cls._ssim_native_ok(x, y, weight, c1, c2, native):
+            return ops.weighted_ssim(x.contiguous(), y.contiguous(), weight.contiguous(), c2, weight_epsilon)
+        return cls._weighted_ssim_torch(x, y, weight, c1, c2, weight_epsilon)
+
+    @classmethod
+    def _weighted_ssim_torch(cls, x, y, weight, c1=float('inf'), c2=9e-6, weight_epsilon=0.01):
         if c1 == float('inf') and c2 == float('inf'):
             raise ValueError('Both c1 and c2 are infinite, SSIM loss is zero. This is likely unintended.')
 
@@ -217,19 +239,37 @@ class network_tools():
         return torch.clamp((1 - n / d) / 2, 0, 1), w_avg
 
     @classmethod
-    def photo_loss_multi_type(cls, x, y, occ_mask, photo_loss_type='abs_robust', photo_loss_delta=0.4, photo_loss_use_occ=False):
+    def photo_loss_multi_type(cls, x, y, occ_mask, photo_loss_type='abs_robust', photo_loss_delta=0.4, photo_loss_use_occ=False,
+                              native=True):
         """model/upflow.py:265-288."""
-        occ_weight = occ_mask
         if photo_loss_type == 'abs_robust':
             # sub / abs / add / pow / mul / sum of the reference as ONE deterministic reduction (csrc/loss.hip)
             s, s_occ = ops.robust_loss_sums(x, y, occ_mask if photo_loss_use_occ else None, q=photo_loss_delta, eps=0.01)
             return s / (s_occ + 1e-6) if photo_loss_use_occ else s / float(x.numel())
-        elif photo_loss_type == 'charbonnier':
+        occ = occ_mask if photo_loss_use_occ else None
+        if photo_loss_type in ('charbonnier', 'L1') and native and x.shape == y.shape and (occ is None or not occ.requires_grad) \
+                and ops.loss_variant_operands_ok(x, y, occ, min_hw=1):
+            # the same reduction with another point-wise kind (csrc/loss_variants.hip: upf_pointwise_loss_*)
+            s, s_occ = ops.pointwise_loss_sums(x.contiguous(), y.contiguous(), None if occ is None else occ.contiguous(),
+                                               kind=photo_loss_type, q=photo_loss_delta)
+            return s / (s_occ + 1e-6) if photo_loss_use_occ else s / float(x.numel())
+        if photo_loss_type == 'SSIM' and cls._ssim_native_ok(x, y, occ_mask, float('inf'), 9e-6, native):
+            # the map is never written: the three sums the two forms divide come out of the one forward launch
+            s_lw, s_w, s_l = ops.ssim_loss_sums(x.contiguous(), y.contiguous(), occ_mask.contiguous())
+            if photo_loss_use_occ:
+                return s_lw / (s_w + 1e-6)
+            return s_l / float(x.shape[0] * x.shape[1] * (x.shape[2] - 2) * (x.shape[3] - 2))
+        return cls._photo_loss_multi_type_torch(x, y, occ_mask, photo_loss_type, photo_loss_delta, photo_loss_use_occ)
+
+    @classmethod
+    def _photo_loss_multi_type_torch(cls, x, y, occ_mask, photo_loss_type, photo_loss_delta=0.4, photo_loss_use_occ=False):
+        occ_weight = occ_mask
+        if photo_loss_type == 'charbonnier':
             loss_diff = ((x - y) ** 2 + 1e-6).pow(photo_loss_delta)
         elif photo_loss_type == 'L1':
             loss_diff = (x - y + 1e-6).abs()
         elif photo_loss_type == 'SSIM':
-            loss_diff, occ_weight = cls.weighted_ssim(x, y, occ_mask)
+            loss_diff, occ_weight = cls._weighted_ssim_torch(x, y, occ_mask)
         else:
             raise ValueError('wrong photo_loss type: %s' % photo_loss_type)
         if photo_loss_use_occ:
@@ -347,15 +387,19 @@ class UPFlow_net(tools.abstract_model):
             s_im2 = F.interpolate(im2, s_f.shape[2:], mode='area')
         else:
             raise ValueError('wrong smooth level choosed: %s' % c.smooth_level)
+        native = not getattr(self, '_no_native_loss_variants', False)      # (True on the module: the torch spelling of every variant)
         smooth = 0
         for order, weight in ((1, c.smooth_order_1_weight), (2, c.smooth_order_2_weight)):
             if weight <= 0:
                 continue
             if c.smooth_type == 'edge':
-                fn = nt.edge_aware_smoothness_order1 if order == 1 else nt.edge_aware_smoothness_order2
-                smooth = smooth + weight * fn(img=s_im1, pred=s_f) + weight * fn(img=s_im2, pred=s_b)
+                if order == 1:
+                    smooth = smooth + weight * nt.edge_aware_smoothness_order1(img=s_im1, pred=s_f) + weight * nt.edge_aware_smoothness_order1(img=s_im2, pred=s_b)
+                else:
+                    smooth = smooth + weight * nt.edge_aware_smoothness_order2(img=s_im1, pred=s_f, native=native) \
+                        + weight * nt.edge_aware_smoothness_order2(img=s_im2, pred=s_b, native=native)
             elif c.smooth_type == 'delta':
-                smooth = smooth + weight * nt.flow_smooth_delta(s_f, order == 2) + weight * nt.flow_smooth_delta(s_b, order == 2)
+                smooth = smooth + weight * nt.flow_smooth_delta(s_f, order == 2, native=native) + weight * nt.flow_smooth_delta(s_b, order == 2, native=native)
             else:
                 raise ValueError('wrong smooth_type: %s' % c.smooth_type)
         out['smooth_loss'] = smooth
@@ -369,7 +413,7 @@ class UPFlow_net(tools.abstract_model):
             im2_warp = tools.torch_warp(im1, flow_b)
         if c.stop_occ_gradient:
             occ_fw, occ_bw = occ_fw.clone().detach(), occ_bw.clone().detach()
-        kw = dict(photo_loss_type=c.photo_loss_type, photo_loss_delta=c.photo_loss_delta, photo_loss_use_occ=c.photo_loss_use_occ)
+        kw = dict(photo_loss_type=c.photo_loss_type, photo_loss_delta=c.photo_loss_delta, photo_loss_use_occ=c.photo_loss_use_occ, native=native)
         out['photo_loss'] = nt.photo_loss_multi_type(im1, im1_warp, occ_fw, **kw) + nt.photo_loss_multi_type(im2, im2_warp, occ_bw, **kw)
         out['im1_warp'], out['im2_warp'] = im1_warp, im2_warp
         # census

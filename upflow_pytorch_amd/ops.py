@@ -1375,6 +1375,253 @@ def smooth_edge1(img, pred):
 
 
 # ------------------------------------------------------------------------------------------------
+# non-default loss variants (csrc/loss_variants.hip, fp32): operands must already be fp32 contiguous NCHW on the GPU
+# ------------------------------------------------------------------------------------------------
+def _lv_check(name, *tensors):
+    for t in tensors:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise UpflowHipError('%s: float32 operands expected, got %s' % (name, t.dtype))
+    return _lib.check_gpu(*tensors)               # (GPU, contiguous, one device)
+
+
+class SmoothEdge2Function(Function):
+    @staticmethod
+    def forward(ctx, img, pred):
+        if img.dim() != 4 or pred.dim() != 4 or img.shape[0] != pred.shape[0] or img.shape[2:] != pred.shape[2:]:
+            raise UpflowHipError('smooth_edge2: img [B,Ci,H,W] and pred [B,Cp,H,W] expected, got %s / %s' % (tuple(img.shape), tuple(pred.shape)))
+        B, Ci, H, W = img.shape
+        Cp = pred.shape[1]
+        if H < 3 or W < 3:
+            raise UpflowHipError('smooth_edge2: at least 3x3 pixels')
+        dev = _lv_check('smooth_edge2', img, pred)
+        nb = _lib.lib().upf_loss_partials(B * H * W)
+        partials = torch.empty((nb, 2), dtype=torch.float32, device=img.device)
+        with torch.cuda.device(dev):
+            _lib.call('upf_smooth_edge2_forward', _lib.ptr(img), _lib.ptr(pred), _lib.ptr(partials), B, Ci, Cp, H, W, _lib.stream_ptr(dev))
+        s = partials.sum(0)
+        ctx.save_for_backward(img, pred)
+        return s[0] / float(B * Cp * (H - 2) * W) + s[1] / float(B * Cp * H * (W - 2))
+
+    @staticmethod
+    def backward(ctx, g):
+        img, pred = ctx.saved_tensors
+        B, Ci, H, W = img.shape
+        Cp = pred.shape[1]
+        gup = _f32(g).reshape(1).contiguous()
+        dev = _lib.check_gpu(img, pred, gup)
+        gp = torch.empty_like(pred)
+        with torch.cuda.device(dev):
+            _lib.call('upf_smooth_edge2_backward', _lib.ptr(img), _lib.ptr(pred), _lib.ptr(gup), _lib.ptr(gp), B, Ci, Cp, H, W, _lib.stream_ptr(dev))
+        return None, gp
+
+
+def smooth_edge2(img, pred):
+    """network_tools.edge_aware_smoothness_order2 (model/upflow.py:220-243) as one reduction launch + one gather backward
+    (differentiable wrt pred; the image is data)."""
+    return SmoothEdge2Function.apply(img, pred)
+
+
+class SmoothDeltaFunction(Function):
+    @staticmethod
+    def forward(ctx, flow, second_order):
+        if flow.dim() != 4:
+            raise UpflowHipError('smooth_delta: a [B,C,H,W] tensor expected, got %s' % (tuple(flow.shape),))
+        B, C, H, W = flow.shape
+        second_order = bool(second_order)
+        m = 3 if second_order else 2
+        if H < m or W < m:
+            raise UpflowHipError('smooth_delta: at least %dx%d pixels' % (m, m))
+        dev = _lv_check('smooth_delta', flow)
+        k = 6 if second_order else 2
+        nb = _lib.lib().upf_loss_partials(B * C * H * W)
+        partials = torch.empty((nb, k), dtype=torch.float32, device=flow.device)
+        with torch.cuda.device(dev):
+            _lib.call('upf_smooth_delta_forward', _lib.ptr(flow), _lib.ptr(partials), B * C, H, W, int(second_order), _lib.stream_ptr(dev))
+        s = partials.sum(0)
+        n = float(B * C)
+        counts = [n * H * (W - 1), n * (H - 1) * W]
+        if second_order:
+            counts += [n * H * (W - 2), n * (H - 1) * (W - 1), n * (H - 1) * (W - 1), n * (H - 2) * W]
+        out = s[0] / counts[0]
+        for i in range(1, k):                                   # the reference's order of the sum of means
+            out = out + s[i] / counts[i]
+        ctx.save_for_backward(flow)
+        ctx.second_order = second_order
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        flow, = ctx.saved_tensors
+        B, C, H, W = flow.shape
+        gup = _f32(g).reshape(1).contiguous()
+        dev = _lib.check_gpu(flow, gup)
+        gf = torch.empty_like(flow)
+        with torch.cuda.device(dev):
+            _lib.call('upf_smooth_delta_backward', _lib.ptr(flow), _lib.ptr(gup), _lib.ptr(gf), B * C, H, W, int(ctx.second_order), _lib.stream_ptr(dev))
+        return gf, None
+
+
+def smooth_delta(flow, second_order=False):
+    """network_tools.flow_smooth_delta (model/upflow.py:245-263): mean |dx| + mean |dy| (+ the four second-difference means) as
+    one reduction launch + one gather backward."""
+    return SmoothDeltaFunction.apply(flow, second_order)
+
+
+POINTWISE_KINDS = {'charbonnier': 0, 'L1': 1}          # UPF_LOSS_CHARBONNIER, UPF_LOSS_L1 (include/upflow_hip.h)
+
+
+class PointwiseLossFunction(Function):
+    @staticmethod
+    def forward(ctx, x, y, occ, kind, q):
+        if kind not in POINTWISE_KINDS:
+            raise UpflowHipError("pointwise_loss: kind must be 'charbonnier' or 'L1', got %r" % (kind,))
+        if x.shape != y.shape or x.dim() != 4:
+            raise UpflowHipError('pointwise_loss: two [B,C,H,W] tensors expected, got %s / %s' % (tuple(x.shape), tuple(y.shape)))
+        B, C, H, W = x.shape
+        if occ is not None and tuple(occ.shape) != (B, 1, H, W):
+            raise UpflowHipError('pointwise_loss: occlusion mask must be [B,1,H,W], got %s' % (tuple(occ.shape),))
+        dev = _lv_check('pointwise_loss', x, y, occ)
+        nb = _lib.lib().upf_loss_partials(B * H * W)
+        partials = torch.empty((nb, 2), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(dev):
+            _lib.call('upf_pointwise_loss_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(partials), B, C, H * W,
+                      POINTWISE_KINDS[kind], float(q), _lib.stream_ptr(dev))
+        sums = partials.sum(0)
+        ctx.save_for_backward(x, y, occ)
+        ctx.cfg = (POINTWISE_KINDS[kind], float(q))
+        s_loss, s_occ = sums.unbind(0)
+        ctx.mark_non_differentiable(s_occ)
+        ctx.set_materialize_grads(False)
+        return s_loss, s_occ
+
+    @staticmethod
+    def backward(ctx, g, _g_occ):
+        if g is None:
+            return None, None, None, None, None
+        if ctx.needs_input_grad[2]:
+            raise UpflowHipError('pointwise_loss: the occlusion weights are treated as constants (hard masks); a mask that '
+                                 'requires grad would silently get a zero gradient')
+        x, y, occ = ctx.saved_tensors
+        kind, q = ctx.cfg
+        B, C, H, W = x.shape
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        if gx is None and gy is None:
+            return None, None, None, None, None
+        coef = _f32(g).reshape(1).contiguous()
+        dev = _lib.check_gpu(x, y, coef)
+        with torch.cuda.device(dev):
+            _lib.call('upf_pointwise_loss_backward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(coef), _lib.ptr(gx), _lib.ptr(gy),
+                      B, C, H * W, kind, q, _lib.stream_ptr(dev))
+        return gx, gy, None, None, None
+
+
+def pointwise_loss_sums(x, y, occ=None, kind='charbonnier', q=0.4):
+    """-> (sum over [B,C,H,W] of loss(x - y) * occ, sum of occ) for the 'charbonnier' ((d^2 + 1e-6)^q) and 'L1' (|d + 1e-6|) arms of
+    network_tools.photo_loss_multi_type (model/upflow.py:273-278, :284-287): ONE deterministic reduction, differentiable wrt x, y."""
+    return PointwiseLossFunction.apply(x, y, occ, kind, q)
+
+
+def _ssim_check(name, x, y, weight, c2, weight_epsilon):
+    if x.shape != y.shape or x.dim() != 4:
+        raise UpflowHipError('%s: two [B,C,H,W] tensors expected, got %s / %s' % (name, tuple(x.shape), tuple(y.shape)))
+    B, C, H, W = x.shape
+    if tuple(weight.shape) != (B, 1, H, W):
+        raise UpflowHipError('%s: weight must be [B,1,H,W], got %s' % (name, tuple(weight.shape)))
+    if H < 3 or W < 3:
+        raise UpflowHipError('%s: at least 3x3 pixels (one window)' % name)
+    if weight.requires_grad:
+        raise UpflowHipError('%s: the gradient wrt the weight is not built (hard masks)' % name)
+    if not (0.0 < float(c2) < float('inf')) or not (0.0 < float(weight_epsilon) < float('inf')):
+        raise UpflowHipError('%s: c2 and weight_epsilon must be positive and finite (c1 = inf form only)' % name)
+    return _lv_check(name, x, y, weight)
+
+
+def _ssim_backward(ctx, gmap, coef_w, coef_u):
+    x, y, weight = ctx.saved_tensors
+    c2, eps = ctx.cfg
+    B, C, H, W = x.shape
+    gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+    if (gx is None and gy is None) or (gmap is None and coef_w is None and coef_u is None):
+        return None, None
+    dev = _lib.check_gpu(x, y, weight, gmap, coef_w, coef_u)
+    with torch.cuda.device(dev):
+        _lib.call('upf_ssim_backward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(gmap), _lib.ptr(coef_w), _lib.ptr(coef_u),
+                  _lib.ptr(gx), _lib.ptr(gy), B, C, H, W, c2, eps, _lib.stream_ptr(dev))
+    return gx, gy
+
+
+class WeightedSsimFunction(Function):
+    @staticmethod
+    def forward(ctx, x, y, weight, c2, weight_epsilon):
+        dev = _ssim_check('weighted_ssim', x, y, weight, c2, weight_epsilon)
+        B, C, H, W = x.shape
+        out = torch.empty((B, C, H - 2, W - 2), dtype=torch.float32, device=x.device)
+        w_avg = torch.empty((B, 1, H - 2, W - 2), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(dev):
+            _lib.call('upf_ssim_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(out), _lib.ptr(w_avg), _lib.ptr(None),
+                      B, C, H, W, float(c2), float(weight_epsilon), _lib.stream_ptr(dev))
+        ctx.save_for_backward(x, y, weight)
+        ctx.cfg = (float(c2), float(weight_epsilon))
+        ctx.mark_non_differentiable(w_avg)
+        ctx.set_materialize_grads(False)
+        return out, w_avg
+
+    @staticmethod
+    def backward(ctx, gmap, _g_wavg):
+        gmap = None if gmap is None else _f32(gmap).contiguous()
+        gx, gy = _ssim_backward(ctx, gmap, None, None)
+        return gx, gy, None, None, None
+
+
+def weighted_ssim(x, y, weight, c2=9e-6, weight_epsilon=0.01):
+    """network_tools.weighted_ssim (model/upflow.py:139-195) with c1 = inf -> (loss map [B,C,H-2,W-2], pooled weight [B,1,H-2,W-2]):
+    one launch forward, one gather launch backward (differentiable wrt x and y; the weight is a constant)."""
+    return WeightedSsimFunction.apply(x, y, weight, c2, weight_epsilon)
+
+
+class SsimLossSumsFunction(Function):
+    @staticmethod
+    def forward(ctx, x, y, weight, c2, weight_epsilon):
+        dev = _ssim_check('ssim_loss_sums', x, y, weight, c2, weight_epsilon)
+        B, C, H, W = x.shape
+        nb = _lib.lib().upf_loss_partials(B * (H - 2) * (W - 2))
+        partials = torch.empty((nb, 3), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(dev):
+            _lib.call('upf_ssim_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(None), _lib.ptr(None), _lib.ptr(partials),
+                      B, C, H, W, float(c2), float(weight_epsilon), _lib.stream_ptr(dev))
+        s_lw, s_w, s_l = partials.sum(0).unbind(0)
+        ctx.save_for_backward(x, y, weight)
+        ctx.cfg = (float(c2), float(weight_epsilon))
+        ctx.mark_non_differentiable(s_w)
+        ctx.set_materialize_grads(False)
+        return s_lw, s_w, s_l
+
+    @staticmethod
+    def backward(ctx, g_lw, _g_w, g_l):
+        coef_w = None if g_lw is None else _f32(g_lw).reshape(1).contiguous()
+        coef_u = None if g_l is None else _f32(g_l).reshape(1).contiguous()
+        gx, gy = _ssim_backward(ctx, None, coef_w, coef_u)
+        return gx, gy, None, None, None
+
+
+def ssim_loss_sums(x, y, weight, c2=9e-6, weight_epsilon=0.01):
+    """-> (sum map * w_avg, sum w_avg, sum map) of weighted_ssim(x, y, weight): what photo_loss_multi_type's 'SSIM' arm
+    (model/upflow.py:279-287) divides — the map is never written; one launch forward, one backward."""
+    return SsimLossSumsFunction.apply(x, y, weight, c2, weight_epsilon)
+
+
+def loss_variant_operands_ok(*tensors, min_hw=2):
+    """The native loss variants apply: every tensor a float32 [B,C,H,W] on the GPU, at least min_hw x min_hw (the callers in
+    model/upflow.py make them contiguous; the operators themselves reject a non-contiguous operand)."""
+    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
+               and t.shape[2] >= min_hw and t.shape[3] >= min_hw for t in tensors if t is not None)
+
+
+# ------------------------------------------------------------------------------------------------
 # convolution under autograd on the matrix cores (training; csrc/conv3x3.hip + csrc/conv_wgrad.hip)
 # ------------------------------------------------------------------------------------------------
 _OPERANDS = OperandCache()      # every packed weight operand of the training path; forms: ('pack', dtype, mode), ('x3', dgrad),

@@ -111,8 +111,16 @@ class loss_functions():
                                        if_use_occ=if_use_occ, averge=averge)
 
     @classmethod
-    def flow_smooth_delta(cls, flow, if_second_order=False):
-        """utils/loss.py:93-111."""
+    def flow_smooth_delta(cls, flow, if_second_order=False, native=True):
+        """utils/loss.py:93-111.  A float32 GPU flow of at least 2x2 (3x3 with the second order) is one reduction launch and one
+        gather backward (csrc/loss_variants.hip: upf_smooth_delta_*); anything else, or native=False, is the torch spelling."""
+        from .. import ops
+        if native and hasattr(ops, 'loss_variant_operands_ok') and ops.loss_variant_operands_ok(flow, min_hw=3 if if_second_order else 2):
+            return ops.smooth_delta(flow.contiguous(), bool(if_second_order))
+        return cls._flow_smooth_delta_torch(flow, if_second_order)
+
+    @classmethod
+    def _flow_smooth_delta_torch(cls, flow, if_second_order=False):
         def grad(x):
             return x[:, :, :, 1:] - x[:, :, :, :-1], x[:, :, 1:] - x[:, :, :-1]
         dx, dy = grad(flow)
