@@ -52,7 +52,8 @@ const char* upf_last_error(void);
  *   elements (0 = 81*H*W) so the volume can be written straight into the first 81 channels of the
  *   115-channel estimator input (model/upflow.py:565).
  *   leaky_slope != 0 fuses LeakyReLU(slope) (model/upflow.py:563-564); 0 = plain correlation.
- * fp32 accumulation for every dtype.
+ * fp32 accumulation for every dtype.  The scale: 16-bit outputs round fp32(sum * fp32(1/C)) once (after the LeakyReLU); an fp32
+ * output is the correctly rounded sum / C.  A non-finite sum gives the Inf / NaN the division would (in fp32 too).
  */
 int upf_corr81_forward(const void* f1, const void* f2, void* out,
                        int B, int C, int H, int W, int dtype,
@@ -135,7 +136,10 @@ int upf_corr_set_option(const char* name, int value);
  * correlation_cuda_kernel.cu:116-300, 396-530):
  *   g1[n,c,y,x] = (1/C) sum_d gO[n,d,y,x]       * f2[n,c,y+dy,x+dx]
  *   g2[n,c,y,x] = (1/C) sum_d gO[n,d,y-dy,x-dx] * f1[n,c,y-dy,x-dx]
- * grad_out : [B,81,H,W] of `dtype` (contiguous);  g1,g2 : [B,C,H,W] of `dtype`. */
+ * grad_out : [B,81,H,W] of `dtype` (contiguous);  g1,g2 : [B,C,H,W] of `dtype`.
+ * Outside the image f2 = 0, as in the forward: a g1 term whose f2 pixel lies outside is gO times that zero — nothing for a
+ * finite gO, NaN for an Inf / NaN one (every kernel, the W < 4 fallback included).  A g2 term whose source pixel (y-dy, x-dx)
+ * lies outside does not exist.  The scale is the product with the fp32 reciprocal of C. */
 int upf_corr81_backward(const void* f1, const void* f2, const void* grad_out, void* g1, void* g2,
                         int B, int C, int H, int W, int dtype, void* stream);
 

@@ -1,6 +1,7 @@
 """Exactly representable operands for the 16-bit convolution kernels (csrc/conv3x3.hip, conv_kernel.hpp, conv_c8.hip, conv_pair.hip,
 conv_wgrad.hip), their fp64 reference, the guard that makes bit equality a fair demand, and the NaN arena the operands live in.
 Shared by tests/test_hip_conv_exact.py (GPU) and tests/test_exact_model_cpu.py (the conditions, no GPU).  Plain torch, no GPU import.
+The last section does the same for the cost-volume kernels (csrc/corr81_*.hip; tests/test_hip_corr_exact.py).
 
 The idea: every operand sits on a grid (an integer multiple of a power of two, few significant bits).  Every product is then a
 multiple of the QUANTUM (the product of the two grid steps) and so is every partial sum, in any order.  If the sum of the ABSOLUTE
@@ -254,6 +255,18 @@ class Arena(object):
             v.copy_(to_c8(fill.to(self.dtype)))
         return v
 
+    def block(self, B, C, H, W, misalign=0, fill=None):
+        """A CONTIGUOUS [B,C,H,W] block (what the cost-volume entry points take; `nchw` is contiguous only for B = 1) whose first
+        element lies `misalign` elements past a 16-byte boundary; 4 KiB of NaN around it like every block."""
+        unit = 16 // self.buf.element_size()
+        assert 0 <= misalign < unit
+        n = B * C * H * W
+        v = self._take(n + misalign, 0, unit)[misalign:].view(B, C, H, W)
+        assert v.is_contiguous() and v.data_ptr() % 16 == misalign * self.buf.element_size()
+        if fill is not None:
+            v.copy_(fill.to(self.dtype))
+        return v
+
     def snapshot(self):
         return self.buf.view(torch.int16).clone()
 
@@ -264,6 +277,24 @@ class Arena(object):
             mask.as_strided(v.size(), v.stride(), v.storage_offset() - self.buf.storage_offset()).fill_(True)
         now = self.buf.view(torch.int16)
         return bool(((now == snap) | mask).all())
+
+
+class Arena32(Arena):
+    """The same arena in fp32 (the cost volume's parity mode): margins of 2048 elements = 8 KiB, bits compared as int32."""
+
+    def __init__(self, device, elems=1 << 20):
+        self.dtype, self.device = torch.float32, torch.device(device)
+        self.buf = torch.full((elems,), float('nan'), dtype=torch.float32, device=self.device)
+        self.cur = 0
+
+    def snapshot(self):
+        return self.buf.view(torch.int32).clone()
+
+    def untouched(self, snap, *written):
+        mask = torch.zeros(self.buf.numel(), dtype=torch.bool, device=self.device)
+        for v in written:
+            mask.as_strided(v.size(), v.stride(), v.storage_offset() - self.buf.storage_offset()).fill_(True)
+        return bool(((self.buf.view(torch.int32) == snap) | mask).all())
 
 
 # ---- the cases (shared with the CPU conditions) ----------------------------------------------------------------------------------
@@ -482,3 +513,232 @@ def shared_case(dtype):
     guard_wgrad([(o['x'], r['gpre']) for o, r in zip(os_, refs)], os_[0]['w'].shape, 1, 1, st['x'], st['gy'] * SLOPE)
     guard_bias([r['gpre'] for r in refs], st['gy'] * SLOPE)
     return levels, os_, refs
+
+
+# ---- the cost volume (csrc/corr81_fwd.hip with its three kernel headers, corr81_bwd.hip) ---------------------------------------------
+# A plain sum of products of two 16-bit tensors, one scale by 1/C (1/(k*k*C) in the general-parameter kernel), one optional
+# LeakyReLU.  Shared by tests/test_hip_corr_exact.py (GPU) and tests/test_exact_model_cpu.py.  Grids: (step, largest magnitude) of
+# the features 'f' and of grad_out 'g'; grad_out * 0.125 stays representable (bf16: multiples of 1/32 up to 1/4, fp16: of 2^-7), so the
+# gradient the autograd function masks with slope 0.125 is exact.  fp32 runs use the same grids.
+CORR_GRIDS = {torch.bfloat16: {'f': (0.125, 2.0), 'g': (0.25, 2.0)}, torch.float16: {'f': (2.0 ** -5, 2.0), 'g': (2.0 ** -4, 2.0)}}
+CORR_R, CORR_D, CORR_ND = 4, 9, 81
+
+# Shapes (B, C, H, W), sized on the dispatch code (launch_fwd / try_allc / allc_pick in csrc/corr81_fwd.hip, upf_corr81_backward in
+# csrc/corr81_bwd.hip): H = 9 / 5 / 6 is no multiple of a tile height (8, 4, 2), W = 40 / 35 crosses the 32- and 16-pixel tiles.
+CORR_C = (5, 32, 96, 196, 208)
+CORR_ALLC = [(2 if C == 32 else 1, C, 9, W) for W in (40, 35) for C in CORR_C]                # aligned and ragged rows; one B = 2 each
+CORR_SMALL = [(1, 5, 6, 20), (1, 32, 5, 13), (2, 5, 5, 4)]
+CORR_OLD = [(1, 5, 9, 40), (2, 32, 9, 40), (1, 33, 9, 40), (1, 96, 9, 40), (1, 33, 9, 35), (1, 33, 6, 20)]     # old_path: MFMA single / multi chunk, chunked
+CORR_DEEP = [(1, 212, 9, 40), (1, 256, 9, 40), (1, 212, 9, 35), (1, 256, 9, 35)]               # C > 208: nothing all-channels fits
+CORR_SHORT = [(1, 5, 5, 1), (2, 33, 5, 3)]                                                   # rows shorter than a staging quad
+CORR_BIG = (8, 48, 40, 128)                                                                  # the smallest grid of >= 160 8x32 tiles with C > 40
+CORR_F32 = [(2, 32, 9, 40), (1, 5, 9, 35), (1, 196, 6, 20), (1, 33, 5, 13), (1, 5, 5, 1), (1, 212, 5, 8)]
+CORR_FWD = list(dict.fromkeys(CORR_ALLC + CORR_SMALL + CORR_OLD + CORR_DEEP + CORR_SHORT + [CORR_BIG] + CORR_F32))
+CORR_BWD_ALIGNED = [(1, 5, 17, 68), (2, 33, 6, 12), (1, 8, 6, 12)]                           # W % 4 == 0; 64-pixel and 16-row tiles crossed; C % 4 != 0
+CORR_BWD_RAGGED = [(1, 5, 6, 5), (2, 8, 5, 13), (1, 33, 17, 26), (1, 4, 5, 67)]
+CORR_BWD_NARROW = [(1, 5, 7, 1), (2, 8, 5, 2), (1, 33, 6, 3)]                                # W < 4: the gather kernel; C = 5, 33: a short last channel block
+CORR_BWD = CORR_BWD_ALIGNED + CORR_BWD_RAGGED + CORR_BWD_NARROW
+CORR_AUTOGRAD = [(2, 32, 4, 16), (1, 33, 9, 13)]                                             # H = 4: the dy = -4 / +4 channels are exact zeros everywhere
+CORR_GENERAL_SHAPE = (2, 6, 20, 28)
+CORR_NF_SHAPES = [(1, 32, 9, 40), (1, 33, 9, 35)]
+CORR_NF_BWD_SHAPES = [(1, 5, 9, 12), (1, 5, 9, 13), (1, 5, 9, 3)]
+
+
+def corr_operands(shape, dtype, go_shape=None, salt=0):
+    """-> f1, f2, grad_out (fp32 CPU tensors on CORR_GRIDS[dtype], exactly representable in it)."""
+    B, C, H, W = shape
+    G = CORR_GRIDS[dtype]
+    gen = torch.Generator().manual_seed(seed_of('corr', tuple(shape), DTYPE_NAMES[dtype], salt))
+    f1, f2 = grid(shape, G['f'][0], G['f'][1], gen), grid(shape, G['f'][0], G['f'][1], gen)
+    go = grid((B, CORR_ND, H, W) if go_shape is None else go_shape, G['g'][0], G['g'][1], gen)
+    for t in (f1, f2, go, go * SLOPE):
+        assert torch.equal(t.to(dtype).float(), t)
+    return f1, f2, go
+
+
+def corr_sums(f1, f2):
+    """S[n, 9 (dy + 4) + (dx + 4), y, x] = sum_c f1[n,c,y,x] * f2[n,c,y+dy,x+dx], f2 = 0 outside: fp64, NOT divided by C."""
+    B, C, H, W = f1.shape
+    a, b = f1.double(), F.pad(f2.double(), (CORR_R,) * 4)
+    S = a.new_zeros(B, CORR_ND, H, W)
+    for dy in range(CORR_D):
+        for dx in range(CORR_D):
+            S[:, dy * CORR_D + dx] = (a * b[:, :, dy:dy + H, dx:dx + W]).sum(1)
+    return S
+
+
+def corr_grad_sums(f1, f2, go):
+    """G1[n,c,y,x] = sum_d gO[n,d,y,x] * f2[n,c,y+dy,x+dx] (f2 = 0 outside: such a term is gO times that zero — nothing for a
+    finite gO, NaN for a non-finite one); G2[n,c,y,x] = sum_d gO[n,d,y-dy,x-dx] * f1[n,c,y-dy,x-dx] over the source pixels that
+    exist.  fp64, not divided by C."""
+    B, C, H, W = f1.shape
+    a, g, bp = f1.double(), go.double(), F.pad(f2.double(), (CORR_R,) * 4)
+    G1 = torch.zeros_like(a)
+    G2p = a.new_zeros(B, C, H + 2 * CORR_R, W + 2 * CORR_R)
+    for dy in range(CORR_D):
+        for dx in range(CORR_D):
+            w = g[:, dy * CORR_D + dx].unsqueeze(1)
+            G1 += w * bp[:, :, dy:dy + H, dx:dx + W]
+            G2p[:, :, dy:dy + H, dx:dx + W] += w * a
+    return G1, G2p[:, :, CORR_R:CORR_R + H, CORR_R:CORR_R + W]
+
+
+def corr_general_sums(f1, f2, pad, k, md, s1, s2):
+    """oracle/ops.py::correlation_general restated in fp64 without its division by k * k * C: padded inputs, kernel radius
+    (k - 1) / 2, displacement radius md / s2, (2 dr + 1)^2 channels of ceil((H + 2 pad - 2 (kr + md)) / s1) rows."""
+    B, C, H, W = f1.shape
+    kr, dr = (k - 1) // 2, md // s2
+    assert md - dr * s2 - kr >= 0, 'the reference reads outside its padded buffer for these parameters'
+    oH, oW = -(-(H + 2 * pad - 2 * (kr + md)) // s1), -(-(W + 2 * pad - 2 * (kr + md)) // s1)
+    ds = 2 * dr + 1
+    p1, p2 = F.pad(f1.double(), (pad,) * 4), F.pad(f2.double(), (pad,) * 4)
+    ys, xs = torch.arange(oH) * s1 + md, torch.arange(oW) * s1 + md
+    chans = []
+    for tj in range(-dr, dr + 1):
+        for ti in range(-dr, dr + 1):
+            acc = 0
+            for j in range(-kr, kr + 1):
+                for i in range(-kr, kr + 1):
+                    acc = acc + (p1[:, :, ys + j][:, :, :, xs + i] * p2[:, :, ys + tj * s2 + j][:, :, :, xs + ti * s2 + i]).sum(1)
+            chans.append(acc)
+    return torch.stack(chans, 1)
+
+
+def corr_general_grad_sums(f1, f2, go, pad, k, md, s1, s2):
+    """The gradients of corr_general_sums wrt f1 and f2 (fp64 autograd: sums of products of grid values, exact like the rest)."""
+    a, b = f1.double().requires_grad_(True), f2.double().requires_grad_(True)
+    return torch.autograd.grad(corr_general_sums(a, b, pad, k, md, s1, s2), (a, b), go.double())
+
+
+def _finite(t):
+    return torch.where(torch.isfinite(t), t, torch.zeros_like(t))
+
+
+def guard_corr(f1, f2, dtype, what='cost volume'):
+    st = CORR_GRIDS[dtype]['f'][0]
+    a, b = _finite(f1), _finite(f2)
+    return guard(what, corr_sums(a.abs(), b.abs()), st * st, (a, st), (b, st))
+
+
+def guard_corr_grads(f1, f2, go, dtype, step_g, what='cost-volume gradients'):
+    st = CORR_GRIDS[dtype]['f'][0]
+    g = _finite(go)
+    A1, A2 = corr_grad_sums(f1.abs(), f2.abs(), g.abs())
+    return guard(what, torch.maximum(A1, A2), st * step_g, (f1, st), (f2, st), (g, step_g))
+
+
+def guard_corr_general(f1, f2, go, params, dtype, what='general cost volume'):
+    st, sg = CORR_GRIDS[dtype]['f'][0], CORR_GRIDS[dtype]['g'][0]
+    top = guard(what, corr_general_sums(f1.abs(), f2.abs(), *params), st * st, (f1, st), (f2, st))
+    if go is not None:
+        A1, A2 = corr_general_grad_sums(f1.abs(), f2.abs(), go.abs(), *params)
+        top = max(top, guard(what + ' gradients', torch.maximum(A1, A2), st * sg, (go, sg)))
+    return top
+
+
+def corr_quotients(S64, n):
+    """The two fp32 spellings of S / n computed from the exact sum: (fp32(S / n), the IEEE quotient; fp32(S * fp32(1 / n)), the
+    product with the correctly rounded fp32 reciprocal).  Equal — and exact — for a power-of-two n.  No double rounding on the way
+    through fp64: S is an integer below 2^24 quanta and n < 2^13, so S / n lies at least 2^-38 (relative) from every fp32 rounding
+    boundary unless it IS one, far more than fp64's 2^-53; S * fp32(1 / n) has at most 48 significant bits and is exact in fp64."""
+    fin = torch.isfinite(S64)
+    assert torch.equal(S64[fin].float().double(), S64[fin]), 'the sum is not exact in fp32: a broken test'
+    r = (torch.ones((), dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)).double()
+    return (S64 / n).float(), (S64 * r).float()
+
+
+def corr_act32(v32, slope):
+    """The kernels' epilogue on the fp32 value, before the one rounding: slope 0 = none; 0.125 exact; 0.1 = slope01_ref's order."""
+    if slope == 0.0:
+        return v32
+    if slope == SLOPE:
+        return torch.where(v32 > 0, v32, v32 * SLOPE)
+    assert slope == 0.1
+    return slope01_ref(v32.double(), torch.float32)
+
+
+def corr_expected(S64, n, slope, dtype):
+    """-> the (two) tensors of `dtype` a correct kernel may give: one RNE of the activated fp32 spelling (fp32: the spelling itself)."""
+    return tuple(corr_act32(q, slope).to(dtype) for q in corr_quotients(S64, n))
+
+
+@functools.lru_cache(maxsize=None)
+def corr_case(shape, dtype):
+    """-> (f1, f2, grad_out, S fp64) of one forward shape, guarded; computed once and shared (nobody writes to them)."""
+    f1, f2, go = corr_operands(shape, dtype)
+    guard_corr(f1, f2, dtype)
+    return f1, f2, go, corr_sums(f1, f2)
+
+
+def corr_mask(S64, slope):
+    """The factor Corr81Function.backward applies: out > 0 ? 1 : slope — the sign of the 16-bit output is the sign of S (no
+    non-zero S / C underflows to zero on these grids), exact zeros take the slope."""
+    return torch.where(S64 > 0, torch.ones((), dtype=torch.float64), torch.full((), float(slope), dtype=torch.float64))
+
+
+@functools.lru_cache(maxsize=None)
+def corr_grad_case(shape, dtype, slope=0.0):
+    """-> (f1, f2, the gradient the backward kernels see [grad_out, masked if slope], G1 fp64, G2 fp64), guarded."""
+    f1, f2, go = corr_operands(shape, dtype)
+    sg = CORR_GRIDS[dtype]['g'][0]
+    gm = go
+    if slope:
+        gm, sg = (go.double() * corr_mask(corr_sums(f1, f2), slope)).float(), sg * slope
+        assert torch.equal(gm.to(dtype).float(), gm)
+    guard_corr_grads(f1, f2, gm, dtype, sg)
+    return (f1, f2, gm) + tuple(corr_grad_sums(f1, f2, gm))
+
+
+@functools.lru_cache(maxsize=None)
+def corr_general_case(params, dtype):
+    """-> (f1, f2, grad_out or None, S, G1 or None, G2 or None) of one general parameter set at CORR_GENERAL_SHAPE, guarded; the
+    gradients where kernel_size 1 and stride1 1 (oracle.ops.correlation_backward_supported)."""
+    pad, k, md, s1, s2 = params
+    probe = corr_general_sums(torch.zeros(CORR_GENERAL_SHAPE), torch.zeros(CORR_GENERAL_SHAPE), *params)
+    f1, f2, go = corr_operands(CORR_GENERAL_SHAPE, dtype, tuple(probe.shape), salt=params)
+    S = corr_general_sums(f1, f2, *params)
+    if k == 1 and s1 == 1:
+        guard_corr_general(f1, f2, go, params, dtype)
+        G1, G2 = corr_general_grad_sums(f1, f2, go, *params)
+        return f1, f2, go, S, G1, G2
+    guard_corr_general(f1, f2, None, params, dtype)
+    return f1, f2, None, S, None, None
+
+
+# non-finite operands: one element each.  Forward kinds: (tensor, value, place); backward: (value, place)
+CORR_NF_FWD = [('f2', 'nan', 'in'), ('f2', 'nan', 'corner'), ('f1', 'inf', 'in'), ('f1', 'inf', 'corner')]
+CORR_NF_BWD = [(v, p) for v in ('nan', 'inf') for p in ('in', 'edge_out', 'edge_in')]
+_NF = {'nan': float('nan'), 'inf': float('inf')}
+
+
+def corr_nonfinite_fwd(shape, dtype, kind):
+    """One NaN in f2 / one +inf in f1 at an interior pixel (n, c, H/2, W/2) or the corner pixel (H-1, W-1, the end of the last row).
+    -> (f1, f2, S fp64, how many outputs are non-finite): a NaN at (y0, x0) of f2 reaches exactly the (d, y, x) with y + dy = y0,
+    x + dx = x0 — one pixel per displacement whose source exists; an inf in f1 all 81 channels of its pixel (inf * 0 = NaN where f2
+    or its zero padding holds a zero: the reference evaluates the same products)."""
+    B, C, H, W = shape
+    which, val, place = kind
+    f1, f2, _ = corr_operands(shape, dtype, salt=('nf',) + tuple(kind))
+    n, c, y0, x0 = (B - 1, C // 2, H // 2, W // 2) if place == 'in' else (0, C - 1, H - 1, W - 1)
+    (f1 if which == 'f1' else f2)[n, c, y0, x0] = _NF[val]
+    guard_corr(f1, f2, dtype)
+    if which == 'f1':
+        count = CORR_ND
+    else:
+        count = sum(0 <= y0 - dy < H for dy in range(-4, 5)) * sum(0 <= x0 - dx < W for dx in range(-4, 5))
+    return f1, f2, corr_sums(f1, f2), count
+
+
+def corr_nonfinite_bwd(shape, dtype, kind):
+    """One NaN / +inf in grad_out[n, d, y, x]: 'in' an interior pixel, d = (dy, dx) = (1, -2); 'edge_out' pixel (0, W-1) with
+    d = (-4, -4), whose f2 pixel and whose g2 target lie outside the image: g1 of that pixel is NaN (gO times the zero f2 holds
+    there), g2 is untouched; 'edge_in' pixel (H-1, 0) with d = (-1, 0), inside.  -> (f1, f2, go, G1, G2, non-finite counts of G1, G2):
+    C elements of g1 (the pixel, every channel); C of g2 (the target pixel) if it exists."""
+    B, C, H, W = shape
+    val, place = kind
+    f1, f2, go = corr_operands(shape, dtype, salt=('nfb',) + tuple(kind))
+    y, x, dy, dx = {'in': (H // 2, W // 2, 1, -2), 'edge_out': (0, W - 1, -4, -4), 'edge_in': (H - 1, 0, -1, 0)}[place]
+    go[B - 1, (dy + 4) * CORR_D + dx + 4, y, x] = _NF[val]
+    guard_corr_grads(f1, f2, go, dtype, CORR_GRIDS[dtype]['g'][0])
+    inside = 0 <= y + dy < H and 0 <= x + dx < W
+    return (f1, f2, go) + tuple(corr_grad_sums(f1, f2, go)) + (C, C if inside else 0)

@@ -153,3 +153,173 @@ def test_arena_poisons_and_watches_everything_outside_the_views():
     assert a.untouched(snap, y) and not a.untouched(snap)
     a.buf[y.storage_offset() - 1] = 0.0                                  # one element in front of the output slice
     assert not a.untouched(snap, y)
+
+
+# ---- the cost volume: the conditions tests/test_hip_corr_exact.py rests on -------------------------------------------------------------
+def _general_sets():
+    import ast
+    import os
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'test_hip_ops.py')).read()
+    node = [n for n in ast.parse(src).body if isinstance(n, ast.Assign) and getattr(n.targets[0], 'id', None) == 'GENERAL_SETS'][0]
+    return ast.literal_eval(node.value)                                  # (the GPU module itself cannot be imported without a GPU package)
+
+
+GENERAL_SETS = _general_sets()
+
+
+@pytest.mark.parametrize('dtype', DT)
+def test_corr_guard_holds_for_every_case(dtype):
+    tops = [em.guard_corr(*em.corr_case(s, dtype)[:2], dtype) for s in em.CORR_FWD]
+    print('%s forward: at most %.3g quanta' % (em.DTYPE_NAMES[dtype], max(tops)))
+    assert max(tops) < em.LIMIT
+    for s in em.CORR_BWD + em.CORR_AUTOGRAD:
+        for slope in (0.0, em.SLOPE):                                    # (corr_grad_case guards; the masked gradient sits on the slope-times-finer grid)
+            f1, f2, gm, G1, G2 = em.corr_grad_case(s, dtype, slope)
+            assert G1.shape == f1.shape and G2.shape == f2.shape
+    for params in GENERAL_SETS:
+        em.corr_general_case(tuple(params), dtype)
+    with pytest.raises(AssertionError):                                  # the guard refuses features off their grid
+        em.guard_corr(em.corr_case(em.CORR_SMALL[0], dtype)[0] + 2.0 ** -9, em.corr_case(em.CORR_SMALL[0], dtype)[1], dtype)
+
+
+@pytest.mark.parametrize('dtype', DT)
+def test_corr_torch_fp32_in_its_own_order_reproduces_the_fp64_sums(dtype):
+    """Another formulation (unfold + batched matrix product; autograd for the gradients), fp32 accumulation in torch's own order:
+    the same bits as the fp64 shifted sums.  (The 6.6 MB case runs the shifted sums in fp32 instead: its unfolded f2 is 640 MB.)"""
+    for s in em.CORR_FWD + em.CORR_BWD:
+        B, C, H, W = s
+        f1, f2, go, S = em.corr_case(s, dtype)
+        if s == em.CORR_BIG:
+            f2p = F.pad(f2, (4,) * 4)
+            got = torch.stack([(f1 * f2p[:, :, dy:dy + H, dx:dx + W]).sum(1) for dy in range(9) for dx in range(9)], 1)
+            assert torch.equal(got.double(), S), s
+            continue
+        a, b = f1.clone().requires_grad_(True), f2.clone().requires_grad_(True)
+        u = F.unfold(b, 9, padding=4).view(B, C, 81, H * W)              # u[n,c,d,p] = f2[n,c,p + d]
+        got = torch.einsum('ncp,ncdp->ndp', a.view(B, C, H * W), u).view(B, 81, H, W)
+        assert torch.equal(got.detach().double(), S), s
+        if s in em.CORR_BWD:
+            _, _, gm, G1, G2 = em.corr_grad_case(s, dtype)
+            g1, g2 = torch.autograd.grad(got, (a, b), gm)
+            assert torch.equal(g1.double(), G1) and torch.equal(g2.double(), G2), s
+    # the general parameter list: the shifted sums at (4,1,4,1,1) ARE the 81-neighbour sums, and fp32 reproduces every set
+    f1, f2, go, S = em.corr_case(em.CORR_SMALL[0], dtype)
+    assert torch.equal(em.corr_general_sums(f1, f2, 4, 1, 4, 1, 1), S)
+    G = em.corr_grad_sums(f1, f2, go)
+    for want, got in zip(G, em.corr_general_grad_sums(f1, f2, go, 4, 1, 4, 1, 1)):
+        assert torch.equal(got, want)
+    for params in GENERAL_SETS:
+        f1, f2, go, S, G1, G2 = em.corr_general_case(tuple(params), dtype)
+        a, b = f1.clone().requires_grad_(True), f2.clone().requires_grad_(True)
+        pad, k, md, s1, s2 = params
+        kr, dr = (k - 1) // 2, md // s2
+        p1, p2 = F.pad(a, (pad,) * 4), F.pad(b, (pad,) * 4)
+        oH, oW = S.shape[2:]
+        chans = []
+        for tj in range(-dr, dr + 1):
+            for ti in range(-dr, dr + 1):
+                y0, x0 = md - kr, md - kr                                 # fp32, strided slices instead of index tensors, patch summed last
+                pa = torch.stack([p1[:, :, y0 + j:y0 + j + (oH - 1) * s1 + 1:s1, x0 + i:x0 + i + (oW - 1) * s1 + 1:s1] for j in range(k) for i in range(k)])
+                pb = torch.stack([p2[:, :, y0 + tj * s2 + j:y0 + tj * s2 + j + (oH - 1) * s1 + 1:s1, x0 + ti * s2 + i:x0 + ti * s2 + i + (oW - 1) * s1 + 1:s1]
+                                  for j in range(k) for i in range(k)])
+                chans.append((pa * pb).sum(2).sum(0))
+        got = torch.stack(chans, 1)
+        assert torch.equal(got.detach().double(), S), params
+        if go is not None:
+            g1, g2 = torch.autograd.grad(got, (a, b), go)
+            assert torch.equal(g1.double(), G1) and torch.equal(g2.double(), G2), params
+
+
+@pytest.mark.parametrize('dtype', DT)
+def test_corr_operands_make_the_stores_round_and_the_two_quotients_agree_in_16_bits(dtype):
+    """Power-of-two C: >= 1 % of the outputs are exact RNE ties.  All cases: >= 5 % need rounding (forward and both gradients).
+    Per case: the two fp32 spellings of S / C (IEEE quotient; product with the rounded reciprocal) round to DIFFERENT 16-bit values
+    in at most 0.1 % of the elements — "either of the two" is no tolerance."""
+    ties = pow2 = rounded = total = grounded = gtotal = 0
+    for s in em.CORR_FWD:
+        C = s[1]
+        S = em.corr_case(s, dtype)[3]
+        qd, qm = em.corr_quotients(S, C)
+        differ16 = float((qd.to(dtype) != qm.to(dtype)).float().mean())
+        differ32 = float((qd != qm).float().mean())
+        if s != em.CORR_BIG:
+            print('%s %s: fp32 spellings differ in %.1f %%, their 16-bit roundings in %.3f %%' % (em.DTYPE_NAMES[dtype], s, 100 * differ32, 100 * differ16))
+        assert differ16 <= 0.001, (s, differ16)
+        if C & (C - 1) == 0:
+            assert differ32 == 0.0 and torch.equal(qd.double() * C, S), s
+            ties += int(em.is_tie(qd, dtype).sum())
+            pow2 += S.numel()
+        rounded += int(em.needs_rounding(qd, dtype).sum())
+        total += S.numel()
+    for s in em.CORR_BWD:
+        for G in em.corr_grad_case(s, dtype)[3:]:
+            q = em.corr_quotients(G, s[1])
+            assert float((q[0].to(dtype) != q[1].to(dtype)).float().mean()) <= 0.001, s
+            grounded += int(em.needs_rounding(q[0], dtype).sum())
+            gtotal += G.numel()
+    print('%s: %.1f %% ties over power-of-two C, %.1f %% of outputs and %.1f %% of gradients need rounding'
+          % (em.DTYPE_NAMES[dtype], 100.0 * ties / pow2, 100.0 * rounded / total, 100.0 * grounded / gtotal))
+    assert ties >= 0.01 * pow2 and rounded >= 0.05 * total and grounded >= 0.05 * gtotal
+    for params in GENERAL_SETS:
+        S = em.corr_general_case(tuple(params), dtype)[3]
+        qd, qm = em.corr_quotients(S, params[1] * params[1] * em.CORR_GENERAL_SHAPE[1])
+        assert float((qd.to(dtype) != qm.to(dtype)).float().mean()) <= 0.001, params
+
+
+@pytest.mark.parametrize('dtype', DT)
+def test_corr_autograd_cases_have_exact_zeros_and_whole_zero_channels(dtype):
+    s = em.CORR_AUTOGRAD[0]
+    f1, f2, gm, G1, G2 = em.corr_grad_case(s, dtype, em.SLOPE)
+    S = em.corr_case(s, dtype)[3]
+    assert s[2] == 4 and bool((S[:, :9] == 0).all()) and bool((S[:, 72:] == 0).all()) and bool((S[:, 9:72] != 0).any())
+    go = em.corr_case(s, dtype)[2]
+    assert torch.equal(gm[:, :9], go[:, :9] * em.SLOPE) and torch.equal(gm[S > 0], go[S > 0])          # zeros take the slope
+    for s in em.CORR_FWD:                                                # the sign of the 16-bit output is the sign of the sum
+        S = em.corr_case(s, dtype)[3]
+        for q in em.corr_expected(S, s[1], 0.0, dtype):
+            assert torch.equal(q == 0, S == 0), s
+
+
+@pytest.mark.parametrize('dtype', DT)
+def test_corr_nonfinite_references_are_what_they_claim(dtype):
+    for s in em.CORR_NF_SHAPES:
+        B, C, H, W = s
+        for kind in em.CORR_NF_FWD:
+            f1, f2, S, count = em.corr_nonfinite_fwd(s, dtype, kind)
+            bad = ~torch.isfinite(S)
+            assert int(bad.sum()) == count and count == {'in': 81, 'corner': 81 if kind[0] == 'f1' else 25}[kind[2]], (s, kind)
+            assert int(bad.sum(1).max()) == (81 if kind[0] == 'f1' else 1)               # f2: at most one pixel per displacement channel
+            if kind[0] == 'f1':
+                assert int(bad.any(1).sum()) == 1                                       # one pixel, all its channels
+                assert bool(torch.isnan(S).any()) or kind[2] == 'in'                    # the corner's padding zeros: inf * 0
+    for s in em.CORR_NF_BWD_SHAPES:
+        for kind in em.CORR_NF_BWD:
+            f1, f2, go, G1, G2, n1, n2 = em.corr_nonfinite_bwd(s, dtype, kind)
+            assert int((~torch.isfinite(G1)).sum()) == n1 == s[1], (s, kind)
+            assert int((~torch.isfinite(G2)).sum()) == n2, (s, kind)
+            assert n2 == (0 if kind[1] == 'edge_out' or (kind[1] == 'in' and s[3] == 3) else s[1]), (s, kind)
+            if kind[1] == 'edge_out':
+                assert bool(torch.isnan(G1[-1, :, 0, s[3] - 1]).all())                    # gO times the zero outside: NaN for inf too
+
+
+def test_arena_block_is_contiguous_misaligned_and_watched():
+    a = em.Arena(torch.float16, 'cpu', 1 << 16)
+    x = a.block(2, 3, 5, 7, misalign=1, fill=torch.ones(2, 3, 5, 7))
+    y = a.block(2, 115, 3, 5)
+    assert x.is_contiguous() and x.data_ptr() % 16 == 2 and y.data_ptr() % 16 == 0 and bool((x == 1).all()) and bool(torch.isnan(y).all())
+    for v in (x, y):
+        off = v.storage_offset() - a.buf.storage_offset()
+        assert bool(torch.isnan(a.buf[off - a.MARGIN:off]).all()) and bool(torch.isnan(a.buf[off + v.numel():off + v.numel() + a.MARGIN]).all())
+    snap = a.snapshot()
+    y[:, :81].fill_(1.0)
+    assert a.untouched(snap, y[:, :81]) and not a.untouched(snap)
+    y[1, 81, 0, 0] = 0.0                                                 # the first channel behind the output slice
+    assert not a.untouched(snap, y[:, :81])
+    b = em.Arena32('cpu', 1 << 15)
+    z = b.block(1, 2, 3, 5, misalign=1)
+    assert z.dtype == torch.float32 and z.data_ptr() % 16 == 4
+    snap = b.snapshot()
+    z.fill_(0.0)
+    assert b.untouched(snap, z) and not b.untouched(snap)
+    b.buf[z.storage_offset() + z.numel()] = 1.0
+    assert not b.untouched(snap, z)

@@ -45,8 +45,11 @@ void corr81_bwd_kernel(const T* __restrict__ f1, const T* __restrict__ f2, const
     const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
     const int q = in ? yy * W + xx : p;
     off[d] = q;
-    // g1: weight gO[d] at the pixel itself; g2: gO[d] at the displaced source pixel
-    wgt[d] = in ? Elem<T>::load(go + (size_t)d * HW + (which ? q : p)) : 0.f;
+    // g1: weight gO[d] at the pixel itself; g2: gO[d] at the displaced source pixel.  A g1 term whose f2 pixel lies outside
+    // is gO[d] times the ZERO f2 holds there (include/upflow_hip.h), as in the tiled kernel below, whose halo is that zero:
+    // a finite gO[d] adds nothing, an Inf / NaN one makes the pixel NaN.  A g2 term whose source pixel lies outside does
+    // not exist.
+    wgt[d] = in ? Elem<T>::load(go + (size_t)d * HW + (which ? q : p)) : (which ? 0.f : 0.f * Elem<T>::load(go + (size_t)d * HW + p));
   }
   const float invC = 1.0f / (float)C;
   const int c0 = blockIdx.y * cpt, c1 = min(C, c0 + cpt);

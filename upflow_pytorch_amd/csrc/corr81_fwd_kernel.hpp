@@ -289,8 +289,9 @@ void corr81_fwd_kernel(const T* __restrict__ f1, const T* __restrict__ f2, T* __
       if constexpr (sizeof(st) == 4) {
         // fp32 output is the parity mode: one Newton step makes acc*invC the correctly rounded acc/C
         // (`reduce_sum / nelems`, correlation_cuda_kernel.cu:108) without a 10-instruction IEEE divide
+        // (an infinite sum has no residual: -inf * C + inf is NaN, and the quotient of +-inf stays +-inf as it does there)
         const float r = __builtin_fmaf(-t, fC, acc[d][p]);
-        t = __builtin_fmaf(r, invC, t);
+        t = (r == r) ? __builtin_fmaf(r, invC, t) : t;
       }
       v[p] = (slope != 0.f) ? fmaxf(t, t * slope) : t;     // LeakyReLU for 0 < slope < 1
     }
