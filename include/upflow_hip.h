@@ -666,6 +666,52 @@ int upf_ssim_backward(const float* x, const float* y, const float* weight, const
                       const float* coef_w, const float* coef_u, float* grad_x, float* grad_y,
                       int B, int C, int H, int W, float c2, float weight_epsilon, void* stream);
 
+/* ---- optimiser step and dynamic loss scaling on the device (csrc/optim.hip) ---------------------------------------------
+ * The reference trains with torch.optim.Adam(lr=1e-4, amsgrad=True, weight_decay=1e-4) (scripts/simple_train.py:121); these
+ * entry points are that update, torch/optim/adam.py in its capturable form, plus the state machine of a GradScaler, as
+ * launches that only enqueue: fp16 training multiplies the gradient fed to backward by a loss scale S, and the check, the
+ * un-scaling, the skipped step and the scale update all happen inside the captured step.
+ *
+ * Multi-tensor launches: one upf_mt_launch is ONE kernel launch over up to UPF_MT_TENSORS fp32 tensors and UPF_MT_BLOCKS
+ * workgroups; workgroup b takes elements [block_chunk[b] * UPF_MT_CHUNK, + UPF_MT_CHUNK) of tensor block_tensor[b].  The
+ * table is a HOST structure that is passed to the kernel by value (the addresses of a captured step's gradients are not
+ * known before the capture, and a host-to-device copy cannot be captured), so it stays under the 4 KB argument limit and a
+ * longer tensor list is split over several launches (ops.mt_plan).  Pointers need 4-byte alignment only (gradients under
+ * DDP are views into bucket storage); numel is any positive count. */
+#define UPF_MT_TENSORS 48
+#define UPF_MT_BLOCKS 256
+#define UPF_MT_CHUNK 16384
+typedef struct {
+  void* param[UPF_MT_TENSORS];
+  void* grad[UPF_MT_TENSORS];
+  void* exp_avg[UPF_MT_TENSORS];
+  void* exp_avg_sq[UPF_MT_TENSORS];
+  void* max_exp_avg_sq[UPF_MT_TENSORS];
+  int numel[UPF_MT_TENSORS];
+  int block_chunk[UPF_MT_BLOCKS];
+  unsigned char block_tensor[UPF_MT_BLOCKS];
+  int n_tensors, n_blocks;
+} upf_mt_launch;
+/* flag[0] = 1 if any element of the launch's gradients is NaN or +-inf (read-only pass; only `grad` and `numel` of the
+ * table are read; a plain store, never cleared here). */
+int upf_grads_nonfinite_check(const upf_mt_launch* launch, int* flag, void* stream);
+/* torch.optim.Adam(amsgrad=True, maximize=False) with L2 weight decay on the launch's tensors, all operands DEVICE scalars:
+ *   g = grad / loss_scale[0] (a power of two: exact) + weight_decay * p;   t = step[0] + 1   (step is NOT advanced here)
+ *   m = lerp(m, g, 1 - beta1);   v = beta2 v + (1 - beta2) g^2;   vmax = max(vmax, v)
+ *   p -= (lr[0] / (1 - beta1^t)) * m / (sqrt(vmax) / sqrt(1 - beta2^t) + eps)
+ * fp32 state, double hyper-parameters, the rounding points of torch's multi-tensor kernel.  flag[0] != 0: nothing is
+ * written (parameters, both moments and the running maximum keep their bits). */
+int upf_adam_amsgrad_step(const upf_mt_launch* launch, const float* lr, const float* step, const float* loss_scale,
+                          const int* flag, double beta1, double beta2, double eps, double weight_decay, void* stream);
+/* The end of a step, one thread (torch.amp.GradScaler.update with a floor):
+ *   flag set:   loss_scale = max(loss_scale * backoff_factor, 1), growth_tracker = 0, skipped_steps += 1
+ *   flag clear: steps[0..nsteps) += 1 (the step counters of the parameter groups), growth_tracker += 1, and when it reaches
+ *               growth_interval: loss_scale *= growth_factor, growth_tracker = 0
+ *   either way flag = 0.   growth_interval <= 0: a FIXED scale (loss_scale and growth_tracker are left alone; a non-finite
+ *   step is still skipped and counted). */
+int upf_loss_scale_update(float* loss_scale, int* growth_tracker, int* skipped_steps, int* flag, float* steps, int nsteps,
+                          float growth_factor, float backoff_factor, int growth_interval, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """upflow_pytorch_amd — MI355X (gfx950) native hot path of UPFlow behind the reference's operator API.
 
     ops                    autograd operators, one hand-written HIP launch each (libupflow_hip.so)
+    optim                  NativeAdam: Adam + amsgrad with the fp16 mode's loss scale kept on the device
     model.upflow           UPFlow_net drop-in shell (same config flags / state_dict keys / dict I/O)
     model.pwc_modules      conv factory, FeatureExtractor, WarpingLayer_no_div, estimators
     model.correlation_package.correlation   Correlation / CorrelationFunction

@@ -28,6 +28,7 @@ SOURCES = [
     ('misc.hip', ['-ffp-contract=off']),
     ('loss.hip', ['-ffp-contract=off']),
     ('loss_variants.hip', ['-ffp-contract=off']),
+    ('optim.hip', ['-ffp-contract=off']),           # (the fp32 operation order of the Adam update is fixed)
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
 # No packed-fp32 VALU instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) anywhere in the library: on MI355X they were

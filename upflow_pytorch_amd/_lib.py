@@ -17,7 +17,7 @@ MASK_NONE, MASK_LITERAL, MASK_ROBUST = 0, 1, 2
 _DTYPES = {torch.float32: UPF_F32, torch.float16: UPF_F16, torch.bfloat16: UPF_BF16}
 
 _c = ctypes
-_vp, _i, _f, _ll = _c.c_void_p, _c.c_int, _c.c_float, _c.c_longlong
+_vp, _i, _f, _ll, _d = _c.c_void_p, _c.c_int, _c.c_float, _c.c_longlong, _c.c_double
 
 # symbol -> argtypes; every function declared in include/upflow_hip.h (tests check the two lists agree)
 SIGNATURES = {
@@ -106,6 +106,9 @@ SIGNATURES = {
     'upf_ssim_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp],
     'upf_div_selftest': [_i, _vp, _vp],
     'upf_occ_check': [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp],
+    'upf_grads_nonfinite_check': [_vp, _vp, _vp],
+    'upf_adam_amsgrad_step': [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp],
+    'upf_loss_scale_update': [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp],
 }
 
 
@@ -113,6 +116,16 @@ SIGNATURES = {
 class WgradLevel(_c.Structure):
     """upf_wgrad_level (include/upflow_hip.h): one use of a shared convolution in a multi-level weight gradient."""
     _fields_ = [('x', _vp), ('x_batch_stride', _ll), ('grad_pre', _vp), ('g_batch_stride', _ll), ('B', _i), ('H', _i), ('W', _i)]
+
+
+MT_TENSORS, MT_BLOCKS, MT_CHUNK = 48, 256, 16384
+
+
+class MtLaunch(_c.Structure):
+    """upf_mt_launch (include/upflow_hip.h): the tensors and workgroups of ONE multi-tensor launch, passed to the kernel by value."""
+    _fields_ = [('param', _vp * MT_TENSORS), ('grad', _vp * MT_TENSORS), ('exp_avg', _vp * MT_TENSORS),
+                ('exp_avg_sq', _vp * MT_TENSORS), ('max_exp_avg_sq', _vp * MT_TENSORS), ('numel', _i * MT_TENSORS),
+                ('block_chunk', _i * MT_BLOCKS), ('block_tensor', _c.c_ubyte * MT_BLOCKS), ('n_tensors', _i), ('n_blocks', _i)]
 
 
 _lib = None

@@ -2507,3 +2507,124 @@ def dense_stack_train(inputs, convs, slope, flow_tail=None):
         params += [w, b]
     args = list(inputs) + ([flow_tail] if flow_tail is not None else []) + params
     return DenseStackTrainFunction.apply(cfg, *args)
+
+
+# ---- optimiser step and loss scaling on the device (csrc/optim.hip) ---------------------------------------------------------
+# The step of optim.NativeAdam: a non-finite check over all gradients, Adam (amsgrad, L2) with the loss scale divided out, and
+# the scale's state machine — launches on the current stream only, so the training step stays one hipGraph.  The tensors'
+# addresses travel by value in the kernel arguments (the gradients of a captured step are allocated DURING the capture, and a
+# host-to-device copy of a pointer table cannot be captured): at most 4 KB per launch, so the planner below splits the tensor
+# list over as many launches as it needs.
+MT_TENSORS, MT_BLOCKS, MT_CHUNK = _lib.MT_TENSORS, _lib.MT_BLOCKS, _lib.MT_CHUNK
+MT_KERNARG_LIMIT = 4096
+_MT_LISTS = ('param', 'grad', 'exp_avg', 'exp_avg_sq', 'max_exp_avg_sq')
+
+
+def mt_plan(sizes, max_tensors=MT_TENSORS, max_blocks=MT_BLOCKS, chunk=MT_CHUNK):
+    """Assign the tensors of `sizes` (element counts) to multi-tensor launches: -> [(tensors, blocks)] per launch, `tensors` the
+    indices into `sizes` the launch's table holds (at most max_tensors) and `blocks` its workgroups (at most max_blocks) as
+    (slot in `tensors`, chunk): workgroup (s, c) takes elements [c * chunk, min((c + 1) * chunk, size)) of tensor tensors[s].
+    Every element of every tensor belongs to exactly one workgroup of one launch; a tensor of more chunks than a launch has
+    workgroups left continues in the next launch; empty tensors get none.  Pure host arithmetic."""
+    launches, tensors, blocks = [], [], []
+    for ti, n in enumerate(sizes):
+        n = int(n)
+        if n < 0 or n >= 2 ** 31:
+            raise UpflowHipError('mt_plan: tensor %d has %d elements (0 .. 2^31 - 1)' % (ti, n))
+        nchunks, c = (n + chunk - 1) // chunk, 0
+        while c < nchunks:
+            if len(blocks) == max_blocks or (len(tensors) == max_tensors and tensors[-1] != ti):
+                launches.append((tensors, blocks))
+                tensors, blocks = [], []
+            if not tensors or tensors[-1] != ti:
+                tensors.append(ti)
+            take = min(nchunks - c, max_blocks - len(blocks))
+            blocks += [(len(tensors) - 1, cc) for cc in range(c, c + take)]
+            c += take
+    if blocks:
+        launches.append((tensors, blocks))
+    return launches
+
+
+def mt_kernarg_bytes():
+    """Bytes of the largest argument block of the multi-tensor kernels (the Adam launch: the table, four double
+    hyper-parameters, four pointers)."""
+    import ctypes
+    return ctypes.sizeof(_lib.MtLaunch) + 4 * 8 + 4 * 8
+
+
+class MtTables():
+    """The launch tables (upf_mt_launch) of one tensor list: built once from the sizes, the addresses filled per list with
+    set() — the parameters and moments when the optimiser state is made, the gradients every step."""
+
+    def __init__(self, sizes):
+        self.sizes = [int(n) for n in sizes]
+        self.launches = []
+        for tensors, blocks in mt_plan(self.sizes):
+            L = _lib.MtLaunch()
+            L.n_tensors, L.n_blocks = len(tensors), len(blocks)
+            for s, ti in enumerate(tensors):
+                L.numel[s] = self.sizes[ti]
+            for b, (s, c) in enumerate(blocks):
+                L.block_tensor[b], L.block_chunk[b] = s, c
+            self.launches.append((L, tensors))
+        self.device = None
+        self.filled = set()
+
+    def set(self, which, tensors):
+        """which: 'param' | 'grad' | 'exp_avg' | 'exp_avg_sq' | 'max_exp_avg_sq'; tensors: fp32, contiguous, on one GPU, of
+        the sizes the tables were planned for (any 4-byte alignment: DDP's gradients are views into bucket storage)."""
+        if which not in _MT_LISTS or len(tensors) != len(self.sizes):
+            raise UpflowHipError('MtTables.set: %r with %d tensors (planned: %d)' % (which, len(tensors), len(self.sizes)))
+        for t, n in zip(tensors, self.sizes):
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.is_sparse:
+                raise UpflowHipError('MtTables.set(%r): every tensor must be a dense contiguous fp32 GPU tensor of the planned size '
+                                     '(got %s %s %s, planned %d elements); there is no CPU path' % (which, t.device, t.dtype, tuple(t.shape), n))
+            if self.device is None:
+                self.device = t.device
+            elif t.device != self.device:
+                raise UpflowHipError('operands on different devices: %s vs %s' % (self.device, t.device))
+        for L, idx in self.launches:
+            arr = getattr(L, which)
+            for s, ti in enumerate(idx):
+                arr[s] = tensors[ti].data_ptr()
+        self.filled.add(which)
+
+
+def _mt_scalar(t, dtype, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.numel() >= 1 and t.is_contiguous()):
+        raise UpflowHipError('%s must be a %s GPU tensor' % (name, dtype))
+    return _lib.ptr(t)
+
+
+def grads_nonfinite_check(tables, flag):
+    """flag (int32 device scalar) = 1 if any gradient element of `tables` is NaN or +-inf; never cleared here."""
+    import ctypes
+    if 'grad' not in tables.filled:
+        raise UpflowHipError('grads_nonfinite_check: the gradients were not set')
+    f = _mt_scalar(flag, torch.int32, 'flag')
+    for L, _ in tables.launches:
+        _lib.call('upf_grads_nonfinite_check', ctypes.byref(L), f, _lib.stream_ptr(tables.device))
+
+
+def adam_amsgrad_step(tables, lr, step, loss_scale, flag, beta1, beta2, eps, weight_decay):
+    """torch.optim.Adam(amsgrad=True) with L2 weight decay on the tensors of `tables`, in place; lr, step (the count BEFORE
+    this step; not advanced here), loss_scale (fp32) and flag (int32) are device scalars; flag != 0: nothing is written."""
+    import ctypes
+    if tables.filled != set(_MT_LISTS):
+        raise UpflowHipError('adam_amsgrad_step: lists not set: %s' % sorted(set(_MT_LISTS) - tables.filled))
+    args = (_mt_scalar(lr, torch.float32, 'lr'), _mt_scalar(step, torch.float32, 'step'),
+            _mt_scalar(loss_scale, torch.float32, 'loss_scale'), _mt_scalar(flag, torch.int32, 'flag'))
+    for L, _ in tables.launches:
+        _lib.call('upf_adam_amsgrad_step', ctypes.byref(L), *args, float(beta1), float(beta2), float(eps), float(weight_decay),
+                  _lib.stream_ptr(tables.device))
+
+
+def loss_scale_update(loss_scale, growth_tracker, skipped_steps, flag, steps, growth_factor, backoff_factor, growth_interval):
+    """The end of a step (one thread): see upf_loss_scale_update.  steps: the fp32 device vector of the parameter groups' step
+    counters, advanced by one on a step that was not skipped; growth_interval <= 0: a fixed scale."""
+    _lib.check_gpu(loss_scale, growth_tracker, skipped_steps, flag, steps)
+    _lib.call('upf_loss_scale_update', _mt_scalar(loss_scale, torch.float32, 'loss_scale'),
+              _mt_scalar(growth_tracker, torch.int32, 'growth_tracker'), _mt_scalar(skipped_steps, torch.int32, 'skipped_steps'),
+              _mt_scalar(flag, torch.int32, 'flag'), _mt_scalar(steps, torch.float32, 'steps'), int(steps.numel()),
+              float(growth_factor), float(backoff_factor), int(growth_interval), _lib.stream_ptr(loss_scale.device))

@@ -44,7 +44,8 @@ class Trainer():
     """net: a module with the UPFlow_net dict contract (input_dict -> output_dict with loss terms)."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-4, scheduler_gamma=1.0, device=None, distributed=None, graph=False,
-                 batch_check='collective', fused_adam=None):
+                 batch_check='collective', fused_adam=None, loss_scale=None, growth_interval=2000, growth_factor=2.0,
+                 backoff_factor=0.5):
         """fused_adam: the optimizer step as ONE multi-tensor kernel (torch.optim.Adam(fused=True): the same update formulas —
         Adam + amsgrad + L2 weight decay, scripts/simple_train.py:119-130 — in one pass over the 80 parameters instead of the
         15 `foreach` launches, 0.23 ms of a 11.8 ms step); default: on a GPU.
@@ -52,7 +53,23 @@ class Trainer():
         (a last partial batch): 'collective' (default) — every step the ranks all-reduce one mismatch bit and, if ANY rank
         mismatches, ALL ranks take that step eagerly (same collective sequence everywhere: DDP's bucket all-reduce + the
         logging all-reduce); 'raise' — no per-step exchange, a mismatching rank raises ValueError.  A single process always
-        decides locally (eager step + a warning)."""
+        decides locally (eager step + a warning).
+        loss_scale: None (default) — no loss scaling, torch.optim.Adam, exactly the step of the other arguments; 'dynamic' — for
+        train_conv_dtype='fp16': the gradient fed to backward is a device scalar S (2^16 at first; every convolution and loss kernel
+        is linear in it) that lifts the activation gradients out of fp16's subnormals, and the optimizer is optim.NativeAdam:
+        non-finite check of the gradients, Adam on grad / S or — on an overflow — no update at all, then S halved (never below 1)
+        or, after growth_interval clean steps, multiplied by growth_factor; all of it kernels on the stream, inside the captured
+        step (torch.amp.GradScaler's defaults and state machine, without its host synchronisation); a positive power of two —
+        that fixed S, non-finite steps still skipped and counted.  The stats gain 'loss_scale' and 'skipped_steps' (the values
+        AFTER the step); `loss` stays the unscaled loss.  GPU only."""
+        from . import optim as _optim
+        from ._lib import UpflowHipError
+        self._loss_scaling = loss_scale is not None
+        if self._loss_scaling:
+            _optim.parse_loss_scale(loss_scale)              # ValueError for anything but 'dynamic' / a positive power of two
+            if device is None or torch.device(device).type != 'cuda':
+                raise UpflowHipError('loss_scale=%r needs a GPU (device=%r): the scaled step is native kernels only, there is no '
+                                     'CPU path' % (loss_scale, device))
         if batch_check not in ('collective', 'raise'):
             raise ValueError("batch_check must be 'collective' or 'raise', got %r" % (batch_check,))
         self.batch_check = batch_check
@@ -86,8 +103,13 @@ class Trainer():
         lr_arg = torch.tensor(float(lr), dtype=torch.float32, device=device) if self.use_graph else lr
         on_gpu = device is not None and torch.device(device).type == 'cuda'
         self.fused_adam = on_gpu if fused_adam is None else bool(fused_adam)
-        self.optimizer = torch.optim.Adam([p for p in self.net.parameters() if p.requires_grad], lr=lr_arg, amsgrad=True,
-                                          weight_decay=weight_decay, capturable=self.use_graph, fused=self.fused_adam)
+        if self._loss_scaling:
+            self.optimizer = _optim.NativeAdam([p for p in self.net.parameters() if p.requires_grad], lr=lr_arg, amsgrad=True,
+                                               weight_decay=weight_decay, loss_scale=loss_scale, growth_interval=growth_interval,
+                                               growth_factor=growth_factor, backoff_factor=backoff_factor)
+        else:
+            self.optimizer = torch.optim.Adam([p for p in self.net.parameters() if p.requires_grad], lr=lr_arg, amsgrad=True,
+                                              weight_decay=weight_decay, capturable=self.use_graph, fused=self.fused_adam)
         # (the `optimizer` setter below registered the version-counter hook on it and took its parameter list)
         self.graph_warmup = 11 if self.distributed else 3
         self._graph = None
@@ -109,9 +131,24 @@ class Trainer():
         (`tr.optimizer = torch.optim.Adam(..., fused=True)`) — gets the hook, and the replay path's parameter list follows it
         (a replaced fused optimizer had neither, and the step kept multiplying by the step-0 packed weights)."""
         from . import ops as _ops
+        if getattr(self, '_loss_scaling', False):
+            # the scale, the overflow flag and the skipped step live in the optimizer: any other one would be fed SCALED gradients
+            from .optim import NativeAdam
+            if not isinstance(opt, NativeAdam):
+                raise TypeError('a Trainer with loss_scale set takes an optim.NativeAdam only, got %s' % type(opt).__name__)
         self._optimizer = opt
         _ops.register_version_hook(opt)
         self._params_flat = [p for g in opt.param_groups for p in g['params']]
+
+    @property
+    def loss_scale(self):
+        """The loss scale S as the device tensor the step reads and updates (None without loss scaling)."""
+        return self._optimizer.loss_scale if self._loss_scaling else None
+
+    @property
+    def skipped_steps(self):
+        """Device int32 count of the steps skipped for a non-finite gradient (None without loss scaling)."""
+        return self._optimizer.skipped_steps if self._loss_scaling else None
 
     def shard(self, batch):
         """This rank's contiguous-strided slice of a GLOBAL batch dict (DistributedSampler-style)."""
@@ -126,7 +163,13 @@ class Trainer():
         batch['if_loss'] = True
         out = self.net(batch)
         loss, parts = self.loss_manager.compute_loss(out)
-        loss.backward()                      # DDP overlaps the gradient all-reduce with the rest of backward
+        if self._loss_scaling:
+            # S seeds the backward pass (a device scalar: no multiply node, and the captured step reads its current value).  Under
+            # DDP the all-reduce averages the SCALED gradients; a NaN / inf on any rank is non-finite on every rank after the
+            # reduction, so each rank's check takes the same decision — skip, back off — with no extra collective.
+            loss.backward(gradient=self.optimizer.loss_scale)
+        else:
+            loss.backward()                  # DDP overlaps the gradient all-reduce with the rest of backward
         self.optimizer.step()
         # (torch._fused_adam_ updates the parameters WITHOUT advancing their autograd version counters, which is what the packed
         # 16-bit weight copies of the convolution path are keyed on — ops.conv_pack_from_master, pwc_modules._PackedConv3x3: the
@@ -138,6 +181,9 @@ class Trainer():
         if self.distributed:                 # loss terms averaged over ranks (one 5-float all-reduce, for logging)
             dist.all_reduce(stats, op=dist.ReduceOp.SUM)
             stats = stats / self.world
+        if self._loss_scaling:               # (the same on every rank: appended after the averaging)
+            self._names = self._names + ['loss_scale', 'skipped_steps']
+            stats = torch.cat([stats, self.optimizer.loss_scale.reshape(1), self.optimizer.skipped_steps.reshape(1).float()])
         return stats
 
     def _capture(self, batch):
