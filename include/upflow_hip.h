@@ -586,7 +586,8 @@ int upf_loss_partials(long long n_pixels);
 /* 'abs_robust' photometric / distillation term, network_tools.photo_loss_multi_type (model/upflow.py:265-288):
  *   partials[k] = { sum (|x - y| + eps)^q * occ,  sum occ }   over workgroup k's pixels, all C channels;
  * x, y [B,C,HW]; occ [B,HW] or NULL (= 1).  Backward: grad_x = coef[0] * occ * q * (|d|+eps)^(q-1) * sign(d),
- * grad_y = -grad_x (either may be NULL); coef is a DEVICE scalar (upstream gradient / the loss's denominator). */
+ * grad_y = -grad_x (either may be NULL); coef is a DEVICE scalar (upstream gradient / the loss's denominator).
+ * (The kernel pair is templated on the point-wise kind; this is its abs_robust instantiation, upf_pointwise_loss_* the others.) */
 int upf_robust_loss_forward(const float* x, const float* y, const float* occ, float* partials,
                             int B, int C, int HW, float eps, float q, void* stream);
 int upf_robust_loss_backward(const float* x, const float* y, const float* occ, const float* coef,
@@ -619,7 +620,7 @@ int upf_smooth_edge1_forward(const float* img, const float* pred, float* partial
 int upf_smooth_edge1_backward(const float* img, const float* pred, const float* grad_up, float* grad_pred,
                               int B, int Ci, int Cp, int H, int W, void* stream);
 
-/* ---- non-default loss variants (csrc/loss_variants.hip); fp32 contiguous NCHW, deterministic, no host synchronisation ---- */
+/* ---- non-default loss variants (csrc/loss_variants.hip; upf_pointwise_loss_*: csrc/loss.hip); fp32 contiguous NCHW, deterministic, no host synchronisation ---- */
 
 /* second-order edge-aware smoothness, network_tools.edge_aware_smoothness_order2 (model/upflow.py:220-243):
  *   xx(i,j) = (p(i,j) - p(i+1,j)) - (p(i+1,j) - p(i+2,j)),  wx(i,j) = exp(-mean_c |img(i,j) - img(i+2,j)|),  i < H-2; columns likewise;
@@ -642,8 +643,8 @@ int upf_smooth_delta_forward(const float* flow, float* partials, int BC, int H, 
 int upf_smooth_delta_backward(const float* flow, const float* grad_up, float* grad_flow, int BC, int H, int W,
                               int second_order, void* stream);
 
-/* point-wise photometric kinds of network_tools.photo_loss_multi_type (model/upflow.py:273-278, :284-287), the shape of
- * upf_robust_loss_*:  UPF_LOSS_CHARBONNIER ((x-y)^2 + 1e-6)^q,  UPF_LOSS_L1 |x - y + 1e-6|  (q unused);
+/* point-wise photometric kinds of network_tools.photo_loss_multi_type (model/upflow.py:273-278, :284-287): the kernel pair of
+ * upf_robust_loss_* with another compile-time kind (csrc/loss.hip):  UPF_LOSS_CHARBONNIER ((x-y)^2 + 1e-6)^q,  UPF_LOSS_L1 |x - y + 1e-6|  (q unused);
  *   partials[k] = { sum loss * occ, sum occ }  (upf_loss_partials(B*HW) pairs; occ [B,HW] or NULL = 1, summed once per pixel).
  * Backward: grad_x = coef[0] * occ * d loss / d (x-y), grad_y = -grad_x (either may be NULL); coef is a DEVICE scalar. */
 enum { UPF_LOSS_CHARBONNIER = 0, UPF_LOSS_L1 = 1 };

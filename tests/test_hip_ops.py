@@ -772,6 +772,44 @@ def test_robust_loss_hip_vs_oracle(hip, shape):
     assert relerr(gx.cpu(), gxw) <= 1e-5 and relerr(gy.cpu(), gyw) <= 1e-5
 
 
+def test_robust_loss_and_smooth_edge1_coerce_operands(hip):
+    """robust_loss_sums and smooth_edge1 take operands that are not fp32 contiguous — (a) bf16, (b) a transposed fp32 view — and
+    give the bits of the `.float().contiguous()` copies; the gradient arrives in the input's dtype and shape and is the fp32
+    gradient converted to it.  (2,3,37,45): 3330 pixels, more than one partial block."""
+    gg = torch.Generator().manual_seed(41)
+    shape = (2, 3, 37, 45)
+    x = torch.rand(shape, generator=gg) - 0.45
+    y = x + 0.1 * torch.randn(shape, generator=gg)
+    occ = (torch.rand(2, 1, 37, 45, generator=gg) > 0.2).float()
+    pred = torch.randn(2, 2, 37, 45, generator=gg) * 2
+
+    def run(x, y, occ, pred, wrt):
+        """-> outputs and gradients wrt the leaves behind x, y, pred; x doubles as the image of the smoothness term"""
+        s, so = hip.robust_loss_sums(x, y, occ)
+        v = hip.smooth_edge1(x.detach(), pred)
+        return (s, so, v), torch.autograd.grad(s / (so + 1e-6) + v, wrt)
+
+    def leaves(ts):
+        return [t.detach().clone().requires_grad_(True) for t in ts]
+
+    variants = {'bf16': (lambda t: dev(t).bfloat16(), lambda t: t, lambda g, t: g.to(torch.bfloat16)),
+                'view': (lambda t: dev(t).transpose(2, 3).contiguous(), lambda t: t.transpose(2, 3), lambda g, t: g.transpose(2, 3))}
+    for tag, (make_leaf, operand, grad_as_leaf) in variants.items():
+        lx, ly, lp = leaves([make_leaf(t) for t in (x, y, pred)])
+        mask = operand(make_leaf(occ))
+        ops_in = [operand(t) for t in (lx, ly, lp)]
+        if tag == 'view':
+            assert not any(t.is_contiguous() for t in ops_in + [mask])
+        out, grads = run(ops_in[0], ops_in[1], mask, ops_in[2], (lx, ly, lp))
+        ref_in = leaves([t.float().contiguous() for t in ops_in])
+        out_ref, grads_ref = run(ref_in[0], ref_in[1], mask.float().contiguous(), ref_in[2], ref_in)
+        for a, b in zip(out, out_ref):
+            assert a.dtype == torch.float32 and torch.equal(a, b), tag
+        for g, g_ref, leaf in zip(grads, grads_ref, (lx, ly, lp)):
+            assert g.dtype == leaf.dtype and g.shape == leaf.shape, tag
+            assert g_ref.dtype == torch.float32 and torch.equal(g, grad_as_leaf(g_ref, leaf)), tag
+
+
 @pytest.mark.parametrize('i', range(2))
 def test_smooth_edge1_hip_golden(hip, i):
     g = load_golden('smooth1_%d' % i)

@@ -1,5 +1,5 @@
 """Loss variants without a GPU: the package's torch spellings against fixtures recorded from the reference's own functions
-(tests/golden/lossvar_*.npz, make_golden_loss_variants.py), the C ABI of csrc/loss_variants.hip, and the CPU routing."""
+(tests/golden/lossvar_*.npz, make_golden_loss_variants.py), the C ABI of csrc/loss_variants.hip (upf_pointwise_loss_*: csrc/loss.hip), and the CPU routing."""
 import ctypes
 
 import pytest

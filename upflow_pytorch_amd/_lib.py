@@ -245,3 +245,9 @@ def call(name, *args):
     rc = getattr(lib(), name)(*args)
     if rc != 0:
         raise UpflowHipError('%s failed (%d): %s' % (name, rc, lib().upf_last_error().decode()))
+
+
+def launch(device, name, *args):
+    """call(name, *args, stream) with `device` current and its current stream as the entry point's last argument."""
+    with torch.cuda.device(device):
+        call(name, *args, stream_ptr(device))

@@ -9,29 +9,17 @@
 //                   sum over a [B,C,H,W] pair of (|x - y| + eps)^q, optionally weighted by a [B,1,H,W] occlusion mask —
 //                   the photometric term and every pyramid-distillation term (:461-487) are this reduction.  The
 //                   reference spells it as sub / abs / add / pow / mul / sum: six passes forward and as many backward.
+//   pointwise_loss  the 'charbonnier' and 'L1' arms of the same function (:273-278, :284-287).  One kernel pair, templated on
+//                   the kind, serves these two and abs_robust; the kind is chosen on the host, never inside a kernel.
 //   smooth_edge1    network_tools.edge_aware_smoothness_order1 (model/upflow.py:197-216): first-order flow differences
 //                   weighted by exp(-mean_c |image difference|), both directions, one launch forward and one backward.
 // Reductions are deterministic: every workgroup writes its partial sum, the partials are summed in fixed order by the
-// caller (a [nblocks, 2] tensor); backward kernels are gathers.  Compiled with -ffp-contract=off.
-#include "common.hpp"
+// caller (a [nblocks, 2] tensor); backward kernels are gathers.  The reduction itself (block_sum, red_blocks), sgn, edge_w and
+// the smoothness forward kernel are in loss_common.hpp, shared with loss_variants.hip.  Compiled with -ffp-contract=off.
+#include "loss_common.hpp"
 
 namespace upf {
 namespace loss {
-
-constexpr int NT = 256;
-
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  float r = 0.f;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) r += sh[k];
-  return r;
-}
 
 // ---- boundary-dilated warp ------------------------------------------------------------------------------------------
 struct BTaps { int o00, o10, o01, o11; float x, y, x0f, x1f, y0f, y1f; };
@@ -91,11 +79,32 @@ void boundary_warp_bwd_kernel(const float* __restrict__ I, const float* __restri
   gflow[((size_t)n * 2 + 1) * hw + p] = gy;
 }
 
-// ---- robust (abs_robust) loss sum --------------------------------------------------------------------------------------
-// partials[block] = { sum_{c,p in block} (|x - y| + eps)^q * occ[p],  sum_{p in block} occ[p] }
+// ---- point-wise photometric loss sums: abs_robust (the default), charbonnier, L1 ---------------------------------------------
+// A kind gives the term of one element, loss(d), and its whole backward product, grad(c, o, d) with c = coef[0], o = the mask
+// value and d = x - y.  Each kind keeps its OWN operation order (they round differently), so the product is not factored out.
+struct AbsRobust {                                   // (|d| + eps)^q with libm's powf
+  static __device__ __forceinline__ float loss(float d, float eps, float q) { return powf(fabsf(d) + eps, q); }
+  static __device__ __forceinline__ float grad(float c, float o, float d, float eps, float q) {
+    return c * o * q * powf(fabsf(d) + eps, q - 1.0f) * sgn(d);
+  }
+};
+constexpr float PW_EPS = 1e-6f;                      // the reference's constant of the two kinds below (eps is unused)
+struct Charbonnier {                                 // (d^2 + 1e-6)^q
+  static __device__ __forceinline__ float loss(float d, float, float q) { return fast_pow(d * d + PW_EPS, q); }
+  static __device__ __forceinline__ float grad(float c, float o, float d, float, float q) {
+    return (c * o) * ((q * fast_pow(d * d + PW_EPS, q - 1.0f)) * (2.0f * d));
+  }
+};
+struct L1 {                                          // |d + 1e-6|  (q is unused)
+  static __device__ __forceinline__ float loss(float d, float, float) { return fabsf(d + PW_EPS); }
+  static __device__ __forceinline__ float grad(float c, float o, float d, float, float) { return (c * o) * sgn(d + PW_EPS); }
+};
+
+// partials[block] = { sum_{c,p in block} loss(x - y) * occ[p],  sum_{p in block} occ[p] }
+template <typename Kind>
 __global__ __launch_bounds__(NT)
-void robust_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ occ,
-                       float* __restrict__ partials, int C, int HW, long long npix, float eps, float q) {
+void pointwise_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ occ,
+                          float* __restrict__ partials, int C, int HW, long long npix, float eps, float q) {
   __shared__ float sh[NT / 64];
   float s = 0.f, so = 0.f;
   for (long long p = blockIdx.x * (long long)NT + threadIdx.x; p < npix; p += (long long)gridDim.x * NT) {
@@ -106,18 +115,19 @@ void robust_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
     const float* xb = x + (size_t)n * C * HW + i;
     const float* yb = y + (size_t)n * C * HW + i;
     float t = 0.f;
-    for (int c = 0; c < C; ++c) t += powf(fabsf(xb[(size_t)c * HW] - (y ? yb[(size_t)c * HW] : 0.f)) + eps, q);
+    for (int c = 0; c < C; ++c) t += Kind::loss(xb[(size_t)c * HW] - yb[(size_t)c * HW], eps, q);
     s += t * o;
   }
-  const float a = block_sum(s, sh), b = block_sum(so, sh);
+  const float a = block_sum<NT>(s, sh), b = block_sum<NT>(so, sh);
   if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
 }
 
-// gx = coef * occ * q * (|d| + eps)^(q-1) * sign(d), gy = -gx   (coef: device scalar = upstream gradient / denominator)
+// gx = coef * occ * d loss / d (x - y), gy = -gx   (coef: device scalar = upstream gradient / denominator)
+template <typename Kind>
 __global__ __launch_bounds__(NT)
-void robust_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ occ,
-                       const float* __restrict__ coef, float* __restrict__ gx, float* __restrict__ gy,
-                       int C, int HW, long long total, float eps, float q) {
+void pointwise_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ occ,
+                          const float* __restrict__ coef, float* __restrict__ gx, float* __restrict__ gy,
+                          int C, int HW, long long total, float eps, float q) {
   const long long e = blockIdx.x * (long long)NT + threadIdx.x;
   if (e >= total) return;
   const long long nc = e / HW;
@@ -125,10 +135,26 @@ void robust_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
   const long long n = nc / C;
   const float d = x[e] - y[e];
   const float o = occ ? occ[n * HW + i] : 1.0f;
-  const float sg = (d > 0.f) ? 1.0f : ((d < 0.f) ? -1.0f : 0.f);
-  const float g = coef[0] * o * q * powf(fabsf(d) + eps, q - 1.0f) * sg;
+  const float g = Kind::grad(coef[0], o, d, eps, q);
   if (gx) gx[e] = g;
   if (gy) gy[e] = -g;
+}
+
+template <typename Kind>
+static int pointwise_fwd(const char* name, const float* x, const float* y, const float* occ, float* partials,
+                         int B, int C, int HW, float eps, float q, void* stream) {
+  const long long npix = (long long)B * HW;
+  hipLaunchKernelGGL(pointwise_fwd_kernel<Kind>, dim3(red_blocks(npix)), dim3(NT), 0, (hipStream_t)stream,
+                     x, y, occ, partials, C, HW, npix, eps, q);
+  return check_launch(name);
+}
+template <typename Kind>
+static int pointwise_bwd(const char* name, const float* x, const float* y, const float* occ, const float* coef,
+                         float* gx, float* gy, int B, int C, int HW, float eps, float q, void* stream) {
+  const long long total = (long long)B * C * HW;
+  hipLaunchKernelGGL(pointwise_bwd_kernel<Kind>, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream,
+                     x, y, occ, coef, gx, gy, C, HW, total, eps, q);
+  return check_launch(name);
 }
 
 // grey = 0.2989 r + 0.5870 g + 0.1140 b, evaluated left to right with separate roundings like the reference's expression
@@ -142,43 +168,7 @@ __global__ void grey_kernel(const float* __restrict__ img, float* __restrict__ o
 }
 
 // ---- first-order edge-aware smoothness ------------------------------------------------------------------------------------
-// partials[block] = { sum |pred(i,j) - pred(i+1,j)| * wx(i,j),  sum |pred(i,j) - pred(i,j+1)| * wy(i,j) }
-__device__ __forceinline__ float edge_w(const float* __restrict__ img, int Ci, int HW, int a, int b) {
-  float s = 0.f;
-  for (int c = 0; c < Ci; ++c) s += fabsf(img[(size_t)c * HW + a] - img[(size_t)c * HW + b]);
-  return expf(-(s / (float)Ci));
-}
-
-__global__ __launch_bounds__(NT)
-void smooth1_fwd_kernel(const float* __restrict__ img, const float* __restrict__ pred, float* __restrict__ partials,
-                        int Ci, int Cp, int H, int W, long long npix) {
-  __shared__ float sh[NT / 64];
-  const int HW = H * W;
-  float sx = 0.f, sy = 0.f;
-  for (long long p = blockIdx.x * (long long)NT + threadIdx.x; p < npix; p += (long long)gridDim.x * NT) {
-    const long long n = p / HW;
-    const int q = (int)(p - n * HW), i = q / W, j = q - i * W;
-    const float* im = img + (size_t)n * Ci * HW;
-    const float* pr = pred + (size_t)n * Cp * HW;
-    if (i + 1 < H) {
-      const float wgt = edge_w(im, Ci, HW, q, q + W);
-      float t = 0.f;
-      for (int c = 0; c < Cp; ++c) t += fabsf(pr[(size_t)c * HW + q] - pr[(size_t)c * HW + q + W]);
-      sx += t * wgt;
-    }
-    if (j + 1 < W) {
-      const float wgt = edge_w(im, Ci, HW, q, q + 1);
-      float t = 0.f;
-      for (int c = 0; c < Cp; ++c) t += fabsf(pr[(size_t)c * HW + q] - pr[(size_t)c * HW + q + 1]);
-      sy += t * wgt;
-    }
-  }
-  const float a = block_sum(sx, sh), b = block_sum(sy, sh);
-  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
-}
-
-__device__ __forceinline__ float sgn(float d) { return (d > 0.f) ? 1.0f : ((d < 0.f) ? -1.0f : 0.f); }
-
+// forward: smooth_fwd_kernel<1> (loss_common.hpp), shared with the second-order form of loss_variants.hip
 // gather: pixel (i,j) appears as the minuend of its own two differences and as the subtrahend of its upper / left ones
 __global__ __launch_bounds__(NT)
 void smooth1_bwd_kernel(const float* __restrict__ img, const float* __restrict__ pred, const float* __restrict__ gup,
@@ -203,11 +193,6 @@ void smooth1_bwd_kernel(const float* __restrict__ img, const float* __restrict__
     if (j > 0) g -= cy * wl * sgn(pc[q - 1] - v);
     gpred[((size_t)n * Cp + c) * HW + q] = g;
   }
-}
-
-static int red_blocks(long long n) {
-  long long b = (n + NT - 1) / NT;
-  return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
 
 }  // namespace loss
@@ -240,10 +225,7 @@ extern "C" int upf_robust_loss_forward(const float* x, const float* y, const flo
   using namespace upf;
   UPF_REQUIRE(x && y && partials, UPF_EINVAL, "robust_loss_forward: null pointer");
   UPF_REQUIRE(B > 0 && C > 0 && HW > 0, UPF_EINVAL, "robust_loss_forward: bad shape");
-  const long long npix = (long long)B * HW;
-  hipLaunchKernelGGL(loss::robust_fwd_kernel, dim3(loss::red_blocks(npix)), dim3(loss::NT), 0, (hipStream_t)stream,
-                     x, y, occ, partials, C, HW, npix, eps, q);
-  return check_launch("robust_loss_forward");
+  return loss::pointwise_fwd<loss::AbsRobust>("robust_loss_forward", x, y, occ, partials, B, C, HW, eps, q, stream);
 }
 
 extern "C" int upf_robust_loss_backward(const float* x, const float* y, const float* occ, const float* coef,
@@ -253,9 +235,30 @@ extern "C" int upf_robust_loss_backward(const float* x, const float* y, const fl
   UPF_REQUIRE(B > 0 && C > 0 && HW > 0, UPF_EINVAL, "robust_loss_backward: bad shape");
   const long long total = (long long)B * C * HW;
   UPF_REQUIRE((total + loss::NT - 1) / loss::NT < (1ll << 31), UPF_EINVAL, "robust_loss_backward: grid too large");
-  hipLaunchKernelGGL(loss::robust_bwd_kernel, dim3((unsigned)((total + loss::NT - 1) / loss::NT)), dim3(loss::NT), 0, (hipStream_t)stream,
-                     x, y, occ, coef, grad_x, grad_y, C, HW, total, eps, q);
-  return check_launch("robust_loss_backward");
+  return loss::pointwise_bwd<loss::AbsRobust>("robust_loss_backward", x, y, occ, coef, grad_x, grad_y, B, C, HW, eps, q, stream);
+}
+
+extern "C" int upf_pointwise_loss_forward(const float* x, const float* y, const float* occ, float* partials,
+                                          int B, int C, int HW, int kind, float q, void* stream) {
+  using namespace upf;
+  UPF_REQUIRE(x && y && partials, UPF_EINVAL, "pointwise_loss_forward: null pointer");
+  UPF_REQUIRE(B > 0 && C > 0 && HW > 0, UPF_EINVAL, "pointwise_loss_forward: bad shape");
+  UPF_REQUIRE(kind == UPF_LOSS_CHARBONNIER || kind == UPF_LOSS_L1, UPF_EINVAL, "pointwise_loss_forward: unknown kind %d", kind);
+  if (kind == UPF_LOSS_CHARBONNIER)
+    return loss::pointwise_fwd<loss::Charbonnier>("pointwise_loss_forward", x, y, occ, partials, B, C, HW, 0.f, q, stream);
+  return loss::pointwise_fwd<loss::L1>("pointwise_loss_forward", x, y, occ, partials, B, C, HW, 0.f, q, stream);
+}
+
+extern "C" int upf_pointwise_loss_backward(const float* x, const float* y, const float* occ, const float* coef,
+                                           float* grad_x, float* grad_y, int B, int C, int HW, int kind, float q, void* stream) {
+  using namespace upf;
+  UPF_REQUIRE(x && y && coef && (grad_x || grad_y), UPF_EINVAL, "pointwise_loss_backward: null pointer");
+  UPF_REQUIRE(B > 0 && C > 0 && HW > 0, UPF_EINVAL, "pointwise_loss_backward: bad shape");
+  UPF_REQUIRE(kind == UPF_LOSS_CHARBONNIER || kind == UPF_LOSS_L1, UPF_EINVAL, "pointwise_loss_backward: unknown kind %d", kind);
+  UPF_REQUIRE(((long long)B * C * HW + loss::NT - 1) / loss::NT < (1ll << 31), UPF_EINVAL, "pointwise_loss_backward: grid too large");
+  if (kind == UPF_LOSS_CHARBONNIER)
+    return loss::pointwise_bwd<loss::Charbonnier>("pointwise_loss_backward", x, y, occ, coef, grad_x, grad_y, B, C, HW, 0.f, q, stream);
+  return loss::pointwise_bwd<loss::L1>("pointwise_loss_backward", x, y, occ, coef, grad_x, grad_y, B, C, HW, 0.f, q, stream);
 }
 
 extern "C" int upf_grey_forward(const float* image, float* grey, int B, int HW, void* stream) {
@@ -273,7 +276,7 @@ extern "C" int upf_smooth_edge1_forward(const float* img, const float* pred, flo
   UPF_REQUIRE(img && pred && partials, UPF_EINVAL, "smooth_edge1_forward: null pointer");
   UPF_REQUIRE(B > 0 && Ci > 0 && Cp > 0 && H > 0 && W > 0, UPF_EINVAL, "smooth_edge1_forward: bad shape");
   const long long npix = (long long)B * H * W;
-  hipLaunchKernelGGL(loss::smooth1_fwd_kernel, dim3(loss::red_blocks(npix)), dim3(loss::NT), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(loss::smooth_fwd_kernel<1>, dim3(loss::red_blocks(npix)), dim3(loss::NT), 0, (hipStream_t)stream,
                      img, pred, partials, Ci, Cp, H, W, npix);
   return check_launch("smooth_edge1_forward");
 }

@@ -4,84 +4,28 @@
 //                   the flow weighted by exp(-mean_c |image difference at stride 2|), both directions.
 //   smooth_delta    network_tools.flow_smooth_delta (model/upflow.py:245-263): mean |first differences|, optionally plus the
 //                   four second differences built from the first ones in the reference's order, each with its own mean.
-//   pointwise_loss  the 'charbonnier' and 'L1' arms of photo_loss_multi_type (model/upflow.py:273-278, :284-287), the shape of
-//                   upf_robust_loss_* (csrc/loss.hip) with a `kind` argument.
-//   ssim            network_tools.weighted_ssim (model/upflow.py:139-195) for c1 = inf, finite c2: nine avg_pool2d calls and
+//   ssim           network_tools.weighted_ssim (model/upflow.py:139-195) for c1 = inf, finite c2: nine avg_pool2d calls and
 //                   ~25 element-wise passes forward (and their backward) of the reference become one launch each way.
 // Conventions of loss.hip: NT threads, every workgroup writes its partial sums (summed in fixed order by the caller), backward
 // kernels are gathers (no float atomics), nothing synchronises with the host.  Compiled with -ffp-contract=off.
+// The reduction core, sgn, edge_w and the smoothness forward kernel come from loss_common.hpp; the 'charbonnier' and 'L1'
+// photometric kinds (upf_pointwise_loss_*) are instantiations of the point-wise kernel pair of loss.hip.
 //
 // The SSIM second moments are evaluated in the centred form  sigma_x = sum_i w_i (x_i - mu_x)^2 / sum_i w_i  over the nine taps
 // of a window (held in LDS), which equals the reference's  wpool(x^2) - mu_x^2  in exact arithmetic because the pooled weights
 // (w + eps) / 9 * 1 / (pool(w) + eps) sum to one — without that expression's cancellation (the fp32 torch composition loses
 // three to four digits there).  The derivative simplifies the same way: d sigma_y / d y_q = 2 w_q (y_q - mu_y) / sum w,
 // d sigma_xy / d y_q = w_q (x_q - mu_x) / sum w  (the terms through mu vanish since sum_i w_i (y_i - mu_y) = 0).
-#include "common.hpp"
+#include "loss_common.hpp"
 
 namespace upf {
 namespace lossv {
 
-constexpr int NT = 256;
+using namespace loss;                             // NT, red_blocks, sgn, edge_w, dd, smooth_fwd_kernel (loss_common.hpp)
 constexpr int TW = 32, TH = 8;                     // SSIM tile (TW * TH == NT)
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  float r = 0.f;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) r += sh[k];
-  return r;
-}
-
-__device__ __forceinline__ float sgn(float d) { return (d > 0.f) ? 1.0f : ((d < 0.f) ? -1.0f : 0.f); }
-
-static int red_blocks(long long n) {
-  long long b = (n + NT - 1) / NT;
-  return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
 // ---- second-order edge-aware smoothness ---------------------------------------------------------------------------------
-__device__ __forceinline__ float edge_w(const float* __restrict__ img, int Ci, int HW, int a, int b) {
-  float s = 0.f;
-  for (int c = 0; c < Ci; ++c) s += fabsf(img[(size_t)c * HW + a] - img[(size_t)c * HW + b]);
-  return expf(-(s / (float)Ci));
-}
-// (p0 - p1) - (p1 - p2): gradient_x(gradient_x(pred)) in the reference's order
-__device__ __forceinline__ float dd(const float* __restrict__ p, int a, int s) { return (p[a] - p[a + s]) - (p[a + s] - p[a + 2 * s]); }
-
-// partials[block] = { sum |xx| * wx over i < H-2,  sum |yy| * wy over j < W-2 }
-__global__ __launch_bounds__(NT)
-void smooth2_fwd_kernel(const float* __restrict__ img, const float* __restrict__ pred, float* __restrict__ partials,
-                        int Ci, int Cp, int H, int W, long long npix) {
-  __shared__ float sh[NT / 64];
-  const int HW = H * W;
-  float sx = 0.f, sy = 0.f;
-  for (long long p = blockIdx.x * (long long)NT + threadIdx.x; p < npix; p += (long long)gridDim.x * NT) {
-    const long long n = p / HW;
-    const int q = (int)(p - n * HW), i = q / W, j = q - i * W;
-    const float* im = img + (size_t)n * Ci * HW;
-    const float* pr = pred + (size_t)n * Cp * HW;
-    if (i + 2 < H) {
-      const float wgt = edge_w(im, Ci, HW, q, q + 2 * W);
-      float t = 0.f;
-      for (int c = 0; c < Cp; ++c) t += fabsf(dd(pr + (size_t)c * HW, q, W));
-      sx += t * wgt;
-    }
-    if (j + 2 < W) {
-      const float wgt = edge_w(im, Ci, HW, q, q + 2);
-      float t = 0.f;
-      for (int c = 0; c < Cp; ++c) t += fabsf(dd(pr + (size_t)c * HW, q, 1));
-      sy += t * wgt;
-    }
-  }
-  const float a = block_sum(sx, sh), b = block_sum(sy, sh);
-  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
-}
-
+// forward: smooth_fwd_kernel<2> (loss_common.hpp), shared with the first-order form of loss.hip
 // gather: pixel (i,j) enters the row terms that start at i, i-1, i-2 with coefficients 1, -2, 1 (columns likewise)
 __global__ __launch_bounds__(NT)
 void smooth2_bwd_kernel(const float* __restrict__ img, const float* __restrict__ pred, const float* __restrict__ gup,
@@ -148,7 +92,7 @@ void delta_fwd_kernel(const float* __restrict__ flow, float* __restrict__ partia
   }
   const int k = second ? 6 : 2;
   for (int t = 0; t < k; ++t) {
-    const float a = block_sum(s[t], sh);
+    const float a = block_sum<NT>(s[t], sh);
     if (threadIdx.x == 0) partials[(size_t)k * blockIdx.x + t] = a;
   }
 }
@@ -190,54 +134,6 @@ void delta_bwd_kernel(const float* __restrict__ flow, const float* __restrict__ 
     if (up && lf) g += c3 * sgn(P.dxdy(i - 1, j - 1)) + c4 * sgn(P.dydx(i - 1, j - 1));
   }
   gflow[e] = g;
-}
-
-// ---- point-wise photometric kinds ---------------------------------------------------------------------------------------
-constexpr float PW_EPS = 1e-6f;
-// x^e for x > 0 through the hardware's log2 / exp2, like the distillation kernel (csrc/sgu_blend.hip: msd_pow)
-__device__ __forceinline__ float pw_pow(float x, float e) { return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)); }
-
-__device__ __forceinline__ float pw_loss(int kind, float d, float q) {
-  return kind == UPF_LOSS_CHARBONNIER ? pw_pow(d * d + PW_EPS, q) : fabsf(d + PW_EPS);
-}
-__device__ __forceinline__ float pw_grad(int kind, float d, float q) {      // d loss / d (x - y)
-  return kind == UPF_LOSS_CHARBONNIER ? (q * pw_pow(d * d + PW_EPS, q - 1.0f)) * (2.0f * d) : sgn(d + PW_EPS);
-}
-
-// partials[block] = { sum_{c,p in block} loss(x - y) * occ[p],  sum_{p in block} occ[p] }
-__global__ __launch_bounds__(NT)
-void pointwise_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ occ,
-                          float* __restrict__ partials, int C, int HW, long long npix, int kind, float q) {
-  __shared__ float sh[NT / 64];
-  float s = 0.f, so = 0.f;
-  for (long long p = blockIdx.x * (long long)NT + threadIdx.x; p < npix; p += (long long)gridDim.x * NT) {
-    const long long n = p / HW;
-    const int i = (int)(p - n * HW);
-    const float o = occ ? occ[p] : 1.0f;
-    so += o;
-    const float* xb = x + (size_t)n * C * HW + i;
-    const float* yb = y + (size_t)n * C * HW + i;
-    float t = 0.f;
-    for (int c = 0; c < C; ++c) t += pw_loss(kind, xb[(size_t)c * HW] - yb[(size_t)c * HW], q);
-    s += t * o;
-  }
-  const float a = block_sum(s, sh), b = block_sum(so, sh);
-  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = a; partials[2 * blockIdx.x + 1] = b; }
-}
-
-__global__ __launch_bounds__(NT)
-void pointwise_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ occ,
-                          const float* __restrict__ coef, float* __restrict__ gx, float* __restrict__ gy,
-                          int C, int HW, long long total, int kind, float q) {
-  const long long e = blockIdx.x * (long long)NT + threadIdx.x;
-  if (e >= total) return;
-  const long long nc = e / HW;
-  const int i = (int)(e - nc * HW);
-  const long long n = nc / C;
-  const float o = occ ? occ[n * HW + i] : 1.0f;
-  const float g = (coef[0] * o) * pw_grad(kind, x[e] - y[e], q);
-  if (gx) gx[e] = g;
-  if (gy) gy[e] = -g;
 }
 
 // ---- weighted SSIM (c1 = inf) -------------------------------------------------------------------------------------------
@@ -353,7 +249,7 @@ void ssim_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, c
     }
   }
   if (partials) {
-    const float a = block_sum(s_lw, sh), b = block_sum(s_w, sh), c = block_sum(s_l, sh);
+    const float a = block_sum<NT>(s_lw, sh), b = block_sum<NT>(s_w, sh), c = block_sum<NT>(s_l, sh);
     if (threadIdx.x == 0) { partials[3 * (size_t)blockIdx.x] = a; partials[3 * (size_t)blockIdx.x + 1] = b; partials[3 * (size_t)blockIdx.x + 2] = c; }
   }
 }
@@ -460,7 +356,7 @@ extern "C" int upf_smooth_edge2_forward(const float* img, const float* pred, flo
   UPF_REQUIRE(img && pred && partials, UPF_EINVAL, "smooth_edge2_forward: null pointer");
   UPF_REQUIRE(B > 0 && Ci > 0 && Cp > 0 && H >= 3 && W >= 3 && (long long)H * W < (1ll << 31), UPF_EINVAL, "smooth_edge2_forward: bad shape");
   const long long npix = (long long)B * H * W;
-  hipLaunchKernelGGL(lossv::smooth2_fwd_kernel, dim3(lossv::red_blocks(npix)), dim3(lossv::NT), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(lossv::smooth_fwd_kernel<2>, dim3(lossv::red_blocks(npix)), dim3(lossv::NT), 0, (hipStream_t)stream,
                      img, pred, partials, Ci, Cp, H, W, npix);
   return check_launch("smooth_edge2_forward");
 }
@@ -507,31 +403,6 @@ extern "C" int upf_smooth_delta_backward(const float* flow, const float* grad_up
   hipLaunchKernelGGL(lossv::delta_bwd_kernel, dim3((unsigned)((total + lossv::NT - 1) / lossv::NT)), dim3(lossv::NT), 0, (hipStream_t)stream,
                      flow, grad_up, grad_flow, H, W, total, second_order ? 1 : 0, inv);
   return check_launch("smooth_delta_backward");
-}
-
-extern "C" int upf_pointwise_loss_forward(const float* x, const float* y, const float* occ, float* partials,
-                                          int B, int C, int HW, int kind, float q, void* stream) {
-  using namespace upf;
-  UPF_REQUIRE(x && y && partials, UPF_EINVAL, "pointwise_loss_forward: null pointer");
-  UPF_REQUIRE(B > 0 && C > 0 && HW > 0, UPF_EINVAL, "pointwise_loss_forward: bad shape");
-  UPF_REQUIRE(kind == UPF_LOSS_CHARBONNIER || kind == UPF_LOSS_L1, UPF_EINVAL, "pointwise_loss_forward: unknown kind %d", kind);
-  const long long npix = (long long)B * HW;
-  hipLaunchKernelGGL(lossv::pointwise_fwd_kernel, dim3(lossv::red_blocks(npix)), dim3(lossv::NT), 0, (hipStream_t)stream,
-                     x, y, occ, partials, C, HW, npix, kind, q);
-  return check_launch("pointwise_loss_forward");
-}
-
-extern "C" int upf_pointwise_loss_backward(const float* x, const float* y, const float* occ, const float* coef,
-                                           float* grad_x, float* grad_y, int B, int C, int HW, int kind, float q, void* stream) {
-  using namespace upf;
-  UPF_REQUIRE(x && y && coef && (grad_x || grad_y), UPF_EINVAL, "pointwise_loss_backward: null pointer");
-  UPF_REQUIRE(B > 0 && C > 0 && HW > 0, UPF_EINVAL, "pointwise_loss_backward: bad shape");
-  UPF_REQUIRE(kind == UPF_LOSS_CHARBONNIER || kind == UPF_LOSS_L1, UPF_EINVAL, "pointwise_loss_backward: unknown kind %d", kind);
-  const long long total = (long long)B * C * HW;
-  UPF_REQUIRE((total + lossv::NT - 1) / lossv::NT < (1ll << 31), UPF_EINVAL, "pointwise_loss_backward: grid too large");
-  hipLaunchKernelGGL(lossv::pointwise_bwd_kernel, dim3((unsigned)((total + lossv::NT - 1) / lossv::NT)), dim3(lossv::NT), 0, (hipStream_t)stream,
-                     x, y, occ, coef, grad_x, grad_y, C, HW, total, kind, q);
-  return check_launch("pointwise_loss_backward");
 }
 
 extern "C" int upf_ssim_forward(const float* x, const float* y, const float* weight, float* map, float* w_avg, float* partials,

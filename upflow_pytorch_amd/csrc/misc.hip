@@ -12,24 +12,12 @@
 #include "sampling.hpp"
 #include "norm_merge.hpp"
 #include "internal.hpp"
+#include "loss_common.hpp"    // block_sum
 
 namespace upf {
 namespace misc {
 
 constexpr int NT = 512;
-
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  float r = 0.f;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) r += sh[k];
-  return r;
-}
 
 // PITCHED planes (round 5): the H rows of a plane are `pitch` elements apart (pitch > W; upf_conv_forward_pitched).  The statistics
 // visit the plane's H*W LOGICAL elements in exactly the order — and with exactly the thread assignment — of the contiguous form
@@ -94,7 +82,7 @@ void normalize_stats_kernel(const T* __restrict__ x, float* __restrict__ ws, int
       } else { const float d = Elem<T>::load(xr + i) - K; s1 += d; s2 += d * d; }
     }
     }
-    const float t1 = block_sum(s1, sh), t2 = block_sum(s2, sh);
+    const float t1 = block_sum<NT>(s1, sh), t2 = block_sum<NT>(s2, sh);
     mean = K + t1 / cnt;
     m2 = fmaxf(t2 - t1 * (t1 / cnt), 0.f);
   } else {
@@ -106,7 +94,7 @@ void normalize_stats_kernel(const T* __restrict__ x, float* __restrict__ ws, int
         for (int k = 0; k < V; ++k) s += v[k];
       } else s += Elem<T>::load(xr + i);
     }
-    mean = block_sum(s, sh) / cnt;
+    mean = block_sum<NT>(s, sh) / cnt;
     float ss = 0.f;
     for (int i = i0 + threadIdx.x * V; i < i1; i += NT * V) {
       if constexpr (VEC) { float v[VecIO<T>::N]; VecIO<T>::load(xr + i, v);
@@ -114,7 +102,7 @@ void normalize_stats_kernel(const T* __restrict__ x, float* __restrict__ ws, int
         for (int k = 0; k < V; ++k) { const float d = v[k] - mean; ss += d * d; }
       } else { const float d = Elem<T>::load(xr + i) - mean; ss += d * d; }
     }
-    m2 = block_sum(ss, sh);
+    m2 = block_sum<NT>(ss, sh);
   }
   if (threadIdx.x == 0) {
     float* w = ws + ((size_t)row * nseg + seg) * 3;
@@ -233,8 +221,8 @@ void normalize_bwd_kernel(const T* __restrict__ y, const T* __restrict__ gy, con
   const T* gr = gy + row * HW;
   float sg = 0.f, sgy = 0.f;
   for (int i = threadIdx.x; i < HW; i += NT) { const float g = Elem<T>::load(gr + i); sg += g; sgy += g * Elem<T>::load(yr + i); }
-  const float mg = block_sum(sg, sh) / (float)HW;
-  const float k = block_sum(sgy, sh) / (float)(HW - 1);
+  const float mg = block_sum<NT>(sg, sh) / (float)HW;
+  const float k = block_sum<NT>(sgy, sh) / (float)(HW - 1);
   const float r = rstd[row];
   T* o = gx + row * HW;
   for (int i = threadIdx.x; i < HW; i += NT)

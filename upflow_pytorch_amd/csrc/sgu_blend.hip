@@ -8,6 +8,7 @@
 // flow_upsample replaces upsample2d_flow_as / upsample_flow (model/pwc_modules.py:77-104).
 // Compiled with -ffp-contract=off.
 #include "sampling.hpp"
+#include "loss_common.hpp"    // block_sum, fast_pow (the distillation term)
 
 namespace upf {
 namespace sgu {
@@ -424,9 +425,6 @@ struct MsdLevels {
   unsigned blk0[MSD_MAXL + 1];
   int n;
 };
-// x^e for x > 0 through the hardware's log2 / exp2 (1 ulp each): the libm powf of the composition is ~60 instructions, and the term
-// is evaluated ~20 M times per direction in the backward (the launch was 122 us, bound by it)
-__device__ __forceinline__ float msd_pow(float x, float e) { return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)); }
 __device__ __forceinline__ float msd_up(const float* __restrict__ xl, int w, const Lerp& ly, const Lerp& lx) {
   const float* s0 = xl + ly.i0 * w; const float* s1 = xl + ly.i1 * w;
   return ly.l0 * (lx.l0 * s0[lx.i0] + lx.l1 * s0[lx.i1]) + ly.l1 * (lx.l0 * s1[lx.i0] + lx.l1 * s1[lx.i1]);       // (upsample_fwd_kernel's expression)
@@ -453,25 +451,14 @@ void msd_fwd_kernel(const MsdLevels L, const float* __restrict__ y, const float*
         const size_t hw = (size_t)L.h[l] * L.w[l];
         const float v0 = msd_up(L.x[l] + (size_t)(n * 2) * hw, L.w[l], ly, lx) * L.rx[l];
         const float v1 = msd_up(L.x[l] + (size_t)(n * 2 + 1) * hw, L.w[l], ly, lx) * L.ry[l];
-        const float t = msd_pow(fabsf(v0 - y0) + eps, q) + msd_pow(fabsf(v1 - y1) + eps, q);
+        const float t = fast_pow(fabsf(v0 - y0) + eps, q) + fast_pow(fabsf(v1 - y1) + eps, q);
         s[l] += t * o;
       }
   }
-  auto bsum = [&](float v) {
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) v += __shfl_xor(v, o2, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = 0.f;
-#pragma unroll
-    for (int k = 0; k < MSD_T / 64; ++k) r += sh[k];
-    return r;
-  };
   float* out = partials + (size_t)blockIdx.x * (MSD_MAXL + 1);
 #pragma unroll
-  for (int l = 0; l < MSD_MAXL; ++l) { const float v = bsum(s[l]); if (threadIdx.x == 0) out[l] = v; }
-  const float v = bsum(so);
+  for (int l = 0; l < MSD_MAXL; ++l) { const float v = block_sum<MSD_T>(s[l], sh); if (threadIdx.x == 0) out[l] = v; }
+  const float v = block_sum<MSD_T>(so, sh);
   if (threadIdx.x == 0) out[MSD_MAXL] = v;
 }
 // out[0] = weight * sum_l S_l / den,  out[1] = den   (den = sum occ + 1e-6, or den_const > 0: the element count without a mask)
@@ -532,14 +519,14 @@ void msd_bwd_kernel(const MsdLevels L, const float* __restrict__ y, const float*
   const int j0 = jlo + cj, j1 = j0 + 256;
   const bool in0 = j0 <= jhi, in1 = j1 <= jhi;
   const Lerp lx0 = make_lerp_scaled(in0 ? j0 : jlo, w, sx), lx1 = make_lerp_scaled(in1 ? j1 : jlo, w, sx);
-  // d/dx of (|x - y| + eps)^q * occ at one label pixel, both components (robust_bwd_kernel's expression without the scalar coefficient)
+  // d/dx of (|x - y| + eps)^q * occ at one label pixel, both components (the abs_robust backward expression of loss.hip without the scalar coefficient)
   auto dterm = [&](const Lerp& ly, const Lerp& lx, int i, int j, float wy, float& a0, float& a1) {
     const size_t pix = (size_t)i * W + j;
     const float o = (oc ? oc[pix] : 1.0f) * q * wy;
     const float d0 = msd_up(x0p, w, ly, lx) * rx - y0p[pix], d1 = msd_up(x0p + hw, w, ly, lx) * ry - y0p[HW + pix];
     const float s0 = (d0 > 0.f) ? 1.0f : ((d0 < 0.f) ? -1.0f : 0.f), s1 = (d1 > 0.f) ? 1.0f : ((d1 < 0.f) ? -1.0f : 0.f);
-    a0 += o * msd_pow(fabsf(d0) + eps, q - 1.0f) * s0;
-    a1 += o * msd_pow(fabsf(d1) + eps, q - 1.0f) * s1;
+    a0 += o * fast_pow(fabsf(d0) + eps, q - 1.0f) * s0;
+    a1 += o * fast_pow(fabsf(d1) + eps, q - 1.0f) * s1;
   };
   float acc[2][2] = {{0.f, 0.f}, {0.f, 0.f}};              // [component][column]
   for (int i = ilo + rg; i <= ihi; i += 4) {

@@ -173,7 +173,7 @@ class network_tools():
         """model/upflow.py:197-216 — one fused reduction launch (csrc/loss.hip: upf_smooth_edge1_*)."""
         return ops.smooth_edge1(img, pred)
 
-    # The non-default variants below run natively (csrc/loss_variants.hip, one launch forward and one backward each) when every
+    # The non-default variants below run natively (csrc/loss_variants.hip; the point-wise kinds csrc/loss.hip; one launch forward and one backward each) when every
     # tensor is float32 on the GPU and at least as large as the stencil; otherwise, or with native=False (`net._no_native_loss_variants
     # = True` makes _losses pass that), they are the torch spelling of the reference, kept as the private _*_torch classmethods.
     @classmethod
@@ -249,7 +249,7 @@ class network_tools():
         occ = occ_mask if photo_loss_use_occ else None
         if photo_loss_type in ('charbonnier', 'L1') and native and x.shape == y.shape and (occ is None or not occ.requires_grad) \
                 and ops.loss_variant_operands_ok(x, y, occ, min_hw=1):
-            # the same reduction with another point-wise kind (csrc/loss_variants.hip: upf_pointwise_loss_*)
+            # the same reduction with another point-wise kind (csrc/loss.hip: upf_pointwise_loss_*, the abs_robust kernel pair with another kind)
             s, s_occ = ops.pointwise_loss_sums(x.contiguous(), y.contiguous(), None if occ is None else occ.contiguous(),
                                                kind=photo_loss_type, q=photo_loss_delta)
             return s / (s_occ + 1e-6) if photo_loss_use_occ else s / float(x.numel())

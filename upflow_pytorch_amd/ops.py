@@ -1123,8 +1123,7 @@ class CensusFunction(Function):
         B, _, H, W = gray1.shape
         dev = _lib.check_gpu(gray1, gray2)
         dist = torch.empty_like(gray1)
-        with torch.cuda.device(dev):
-            _lib.call('upf_census_forward', _lib.ptr(gray1), _lib.ptr(gray2), _lib.ptr(dist), B, H, W, int(max_distance), _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_census_forward', _lib.ptr(gray1), _lib.ptr(gray2), _lib.ptr(dist), B, H, W, int(max_distance))
         ctx.save_for_backward(gray1, gray2)
         ctx.max_distance = int(max_distance)
         return dist
@@ -1139,9 +1138,8 @@ class CensusFunction(Function):
         g2 = torch.empty_like(gray2) if ctx.needs_input_grad[1] else None
         if g1 is None and g2 is None:
             return None, None, None
-        with torch.cuda.device(dev):
-            _lib.call('upf_census_backward', _lib.ptr(gray1), _lib.ptr(gray2), _lib.ptr(g), _lib.ptr(g1), _lib.ptr(g2), B, H, W,
-                      ctx.max_distance, _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_census_backward', _lib.ptr(gray1), _lib.ptr(gray2), _lib.ptr(g), _lib.ptr(g1), _lib.ptr(g2), B, H, W,
+                    ctx.max_distance)
         return g1, g2, None
 
 
@@ -1151,8 +1149,31 @@ def census_distance(gray1, gray2, max_distance=3):
 
 
 # ------------------------------------------------------------------------------------------------
-# loss-side operators of the unsupervised training step (csrc/loss.hip, fp32)
+# loss-side operators of the unsupervised training step (csrc/loss.hip, csrc/loss_variants.hip; fp32)
 # ------------------------------------------------------------------------------------------------
+def _lv_check(name, *tensors):
+    """Strict operands: float32, contiguous, on one GPU (None is skipped); -> the device."""
+    for t in tensors:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise UpflowHipError('%s: float32 operands expected, got %s' % (name, t.dtype))
+    return _lib.check_gpu(*tensors)               # (GPU, contiguous, one device)
+
+
+def _partial_sums(dev, name, n, k, tensors, *scalars):
+    """A deterministic reduction over n elements: the forward entry point `name(*tensors, partials, *scalars)` writes k partial
+    sums per workgroup (upf_loss_partials(n) of them), which are added here in fixed order -> the k sums, on the device."""
+    partials = torch.empty((_lib.lib().upf_loss_partials(n), k), dtype=torch.float32, device=dev)
+    _lib.launch(dev, name, *[_lib.ptr(t) for t in tensors], _lib.ptr(partials), *scalars)
+    return partials.sum(0)
+
+
+def _grad_scalar(g):
+    """The upstream gradient of a scalar output as the one-element fp32 device array that the backward kernels read."""
+    return _f32(g).reshape(1).contiguous()
+
+
 class BoundaryWarpFunction(Function):
     @staticmethod
     def forward(ctx, image, flow, start):
@@ -1170,9 +1191,7 @@ class BoundaryWarpFunction(Function):
         h, w = flow.shape[2:]
         dev = _lib.check_gpu(image, flow, start)
         out = torch.empty((B, C, h, w), dtype=torch.float32, device=flow.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_boundary_warp_forward', _lib.ptr(image), _lib.ptr(flow), _lib.ptr(start), _lib.ptr(out), B, C, Hi, Wi, h, w,
-                      _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_boundary_warp_forward', _lib.ptr(image), _lib.ptr(flow), _lib.ptr(start), _lib.ptr(out), B, C, Hi, Wi, h, w)
         ctx.save_for_backward(image, flow, start)
         return out
 
@@ -1186,9 +1205,8 @@ class BoundaryWarpFunction(Function):
         g = _f32(g).contiguous()
         dev = _lib.check_gpu(image, flow, g)
         gflow = torch.empty_like(flow)
-        with torch.cuda.device(dev):
-            _lib.call('upf_boundary_warp_backward', _lib.ptr(image), _lib.ptr(flow), _lib.ptr(start), _lib.ptr(g), _lib.ptr(gflow),
-                      B, C, Hi, Wi, h, w, _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_boundary_warp_backward', _lib.ptr(image), _lib.ptr(flow), _lib.ptr(start), _lib.ptr(g), _lib.ptr(gflow),
+                    B, C, Hi, Wi, h, w)
         return None, gflow, None
 
 
@@ -1197,27 +1215,27 @@ def boundary_warp(image, flow, start):
     return BoundaryWarpFunction.apply(image, flow, start)
 
 
-class RobustLossFunction(Function):
+POINTWISE_KINDS = {'charbonnier': 0, 'L1': 1}          # UPF_LOSS_CHARBONNIER, UPF_LOSS_L1 (include/upflow_hip.h)
+
+
+class PointwiseLossFunction(Function):
+    """(sum over [B,C,H,W] of loss(x - y) * occ, sum of occ) for the kinds 'abs_robust' (upf_robust_loss_*), 'charbonnier' and 'L1'
+    (upf_pointwise_loss_*): one kernel pair templated on the kind (csrc/loss.hip).  Strict: fp32 contiguous GPU operands."""
+
     @staticmethod
-    def forward(ctx, x, y, occ, q, eps):
-        x = _f32(x).contiguous()
-        y = _f32(y).contiguous()
+    def forward(ctx, x, y, occ, kind, q, eps):
+        name = 'robust_loss' if kind == 'abs_robust' else 'pointwise_loss'
         if x.shape != y.shape or x.dim() != 4:
-            raise UpflowHipError('robust_loss: two [B,C,H,W] tensors expected, got %s / %s' % (tuple(x.shape), tuple(y.shape)))
+            raise UpflowHipError('%s: two [B,C,H,W] tensors expected, got %s / %s' % (name, tuple(x.shape), tuple(y.shape)))
         B, C, H, W = x.shape
-        if occ is not None:
-            occ = _f32(occ).contiguous()
-            if tuple(occ.shape) != (B, 1, H, W):
-                raise UpflowHipError('robust_loss: occlusion mask must be [B,1,H,W], got %s' % (tuple(occ.shape),))
-        dev = _lib.check_gpu(x, y, occ)
-        nb = _lib.lib().upf_loss_partials(B * H * W)
-        partials = torch.empty((nb, 2), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_robust_loss_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(partials), B, C, H * W, float(eps), float(q),
-                      _lib.stream_ptr(dev))
-        sums = partials.sum(0)                               # fixed order: deterministic
+        if occ is not None and tuple(occ.shape) != (B, 1, H, W):
+            raise UpflowHipError('%s: occlusion mask must be [B,1,H,W], got %s' % (name, tuple(occ.shape)))
+        dev = _lv_check(name, x, y, occ)
+        # the two entry-point families differ in one argument: eps (abs_robust; the other kinds fix 1e-6) or the kind's code
+        ctx.name = name
+        ctx.scalars = (B, C, H * W, float(eps) if kind == 'abs_robust' else POINTWISE_KINDS[kind], float(q))
+        sums = _partial_sums(dev, 'upf_%s_forward' % name, B * H * W, 2, (x, y, occ), *ctx.scalars)
         ctx.save_for_backward(x, y, occ)
-        ctx.qe = (float(q), float(eps))
         s_loss, s_occ = sums.unbind(0)                       # (mark and return the SAME view objects: ADVICE r2)
         ctx.mark_non_differentiable(s_occ)
         ctx.set_materialize_grads(False)                     # (no zero tensor for s_occ's gradient)
@@ -1226,29 +1244,27 @@ class RobustLossFunction(Function):
     @staticmethod
     def backward(ctx, g, _g_occ):
         if g is None:
-            return None, None, None, None, None
-        if len(ctx.needs_input_grad) > 2 and ctx.needs_input_grad[2]:
-            raise UpflowHipError('robust_loss: the occlusion weights are treated as constants (hard masks); a mask that '
-                                 'requires grad would silently get a zero gradient')
+            return (None,) * 6
+        if ctx.needs_input_grad[2]:
+            raise UpflowHipError('%s: the occlusion weights are treated as constants (hard masks); a mask that '
+                                 'requires grad would silently get a zero gradient' % ctx.name)
         x, y, occ = ctx.saved_tensors
-        q, eps = ctx.qe
-        B, C, H, W = x.shape
-        coef = _f32(g).reshape(1).contiguous()
-        dev = _lib.check_gpu(x, y, coef)
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
         if gx is None and gy is None:
-            return None, None, None, None, None
-        with torch.cuda.device(dev):
-            _lib.call('upf_robust_loss_backward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(coef), _lib.ptr(gx), _lib.ptr(gy),
-                      B, C, H * W, eps, q, _lib.stream_ptr(dev))
-        return gx, gy, None, None, None
+            return (None,) * 6
+        coef = _grad_scalar(g)
+        dev = _lib.check_gpu(x, y, coef)
+        _lib.launch(dev, 'upf_%s_backward' % ctx.name, _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(coef), _lib.ptr(gx), _lib.ptr(gy),
+                    *ctx.scalars)
+        return gx, gy, None, None, None, None
 
 
 def robust_loss_sums(x, y, occ=None, q=0.4, eps=0.01):
     """-> (sum over [B,C,H,W] of (|x - y| + eps)^q * occ, sum of occ): the 'abs_robust' term of
     network_tools.photo_loss_multi_type (model/upflow.py:265-288) as ONE deterministic reduction (differentiable wrt x, y)."""
-    return RobustLossFunction.apply(x, y, occ, q, eps)
+    occ = None if occ is None else _f32(occ).contiguous()
+    return PointwiseLossFunction.apply(_f32(x).contiguous(), _f32(y).contiguous(), occ, 'abs_robust', q, eps)
 
 
 def grey(image):
@@ -1259,8 +1275,7 @@ def grey(image):
         raise UpflowHipError('grey: an RGB image [B,3,H,W] expected, got %s' % (tuple(image.shape),))
     dev = _lib.check_gpu(image)
     out = torch.empty((B, 1, H, W), dtype=torch.float32, device=image.device)
-    with torch.cuda.device(dev):
-        _lib.call('upf_grey_forward', _lib.ptr(image), _lib.ptr(out), B, H * W, _lib.stream_ptr(dev))
+    _lib.launch(dev, 'upf_grey_forward', _lib.ptr(image), _lib.ptr(out), B, H * W)
     return out
 
 
@@ -1293,9 +1308,8 @@ class MsdUpupFunction(Function):
         xp = (_lib._vp * n)(*[x.data_ptr() for x in xs])
         hs = (_lib._c.c_int * n)(*[x.shape[2] for x in xs])
         ws = (_lib._c.c_int * n)(*[x.shape[3] for x in xs])
-        with torch.cuda.device(dev):
-            _lib.call('upf_msd_upup_forward', xp, hs, ws, n, _lib.ptr(y), _lib.ptr(occ), _lib.ptr(partials), _lib.ptr(out2), B, H, W,
-                      float(weight), float(eps), float(q), _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_msd_upup_forward', xp, hs, ws, n, _lib.ptr(y), _lib.ptr(occ), _lib.ptr(partials), _lib.ptr(out2), B, H, W,
+                    float(weight), float(eps), float(q))
         ctx.save_for_backward(y, occ, out2, *xs)
         ctx.cfg = (float(weight), float(q), float(eps))
         ctx.set_materialize_grads(False)
@@ -1310,16 +1324,15 @@ class MsdUpupFunction(Function):
         xs = ctx.saved_tensors[3:]
         weight, q, eps = ctx.cfg
         B, _, H, W = y.shape
-        g = _f32(g).reshape(1).contiguous()
+        g = _grad_scalar(g)
         dev = _lib.check_gpu(y, g)
         gxs = [torch.empty_like(x) for x in xs]
         xp = (_lib._vp * n)(*[x.data_ptr() for x in xs])
         gp = (_lib._vp * n)(*[x.data_ptr() for x in gxs])
         hs = (_lib._c.c_int * n)(*[x.shape[2] for x in xs])
         ws = (_lib._c.c_int * n)(*[x.shape[3] for x in xs])
-        with torch.cuda.device(dev):
-            _lib.call('upf_msd_upup_backward', xp, gp, hs, ws, n, _lib.ptr(y), _lib.ptr(occ), _lib.ptr(g), _lib.ptr(out2), B, H, W,
-                      weight, eps, q, _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_msd_upup_backward', xp, gp, hs, ws, n, _lib.ptr(y), _lib.ptr(occ), _lib.ptr(g), _lib.ptr(out2), B, H, W,
+                    weight, eps, q)
         return (None, None, None, None, None) + tuple(gx if ctx.needs_input_grad[5 + i] else None for i, gx in enumerate(gxs))
 
 
@@ -1336,91 +1349,49 @@ def msd_upup_loss(levels, y, occ=None, weight=1.0, q=0.4, eps=0.01):
     return MsdUpupFunction.apply(y, occ, weight, q, eps, *levels)
 
 
-class SmoothEdge1Function(Function):
+class SmoothEdgeFunction(Function):
+    """Edge-aware smoothness of first (upf_smooth_edge1_*) or second (upf_smooth_edge2_*) order: one forward kernel templated on
+    the order (csrc/loss_common.hpp), one gather backward per order.  Strict: fp32 contiguous GPU operands."""
+
     @staticmethod
-    def forward(ctx, img, pred):
-        img = _f32(img).contiguous()
-        pred = _f32(pred).contiguous()
+    def forward(ctx, img, pred, order):
+        name = 'smooth_edge%d' % order
         if img.dim() != 4 or pred.dim() != 4 or img.shape[0] != pred.shape[0] or img.shape[2:] != pred.shape[2:]:
-            raise UpflowHipError('smooth_edge1: img [B,Ci,H,W] and pred [B,Cp,H,W] expected, got %s / %s' % (tuple(img.shape), tuple(pred.shape)))
+            raise UpflowHipError('%s: img [B,Ci,H,W] and pred [B,Cp,H,W] expected, got %s / %s' % (name, tuple(img.shape), tuple(pred.shape)))
         B, Ci, H, W = img.shape
         Cp = pred.shape[1]
-        if H < 2 or W < 2:
-            raise UpflowHipError('smooth_edge1: at least 2x2 pixels')
-        dev = _lib.check_gpu(img, pred)
-        nb = _lib.lib().upf_loss_partials(B * H * W)
-        partials = torch.empty((nb, 2), dtype=torch.float32, device=img.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_smooth_edge1_forward', _lib.ptr(img), _lib.ptr(pred), _lib.ptr(partials), B, Ci, Cp, H, W, _lib.stream_ptr(dev))
-        s = partials.sum(0)
+        if H <= order or W <= order:
+            raise UpflowHipError('%s: at least %dx%d pixels' % (name, order + 1, order + 1))
+        dev = _lv_check(name, img, pred)
+        s = _partial_sums(dev, 'upf_%s_forward' % name, B * H * W, 2, (img, pred), B, Ci, Cp, H, W)
         ctx.save_for_backward(img, pred)
-        return s[0] / float(B * Cp * (H - 1) * W) + s[1] / float(B * Cp * H * (W - 1))
+        ctx.name = name
+        return s[0] / float(B * Cp * (H - order) * W) + s[1] / float(B * Cp * H * (W - order))
 
     @staticmethod
     def backward(ctx, g):
         img, pred = ctx.saved_tensors
         B, Ci, H, W = img.shape
         Cp = pred.shape[1]
-        gup = _f32(g).reshape(1).contiguous()
+        gup = _grad_scalar(g)
         dev = _lib.check_gpu(img, pred, gup)
         gp = torch.empty_like(pred)
-        with torch.cuda.device(dev):
-            _lib.call('upf_smooth_edge1_backward', _lib.ptr(img), _lib.ptr(pred), _lib.ptr(gup), _lib.ptr(gp), B, Ci, Cp, H, W, _lib.stream_ptr(dev))
-        return None, gp
+        _lib.launch(dev, 'upf_%s_backward' % ctx.name, _lib.ptr(img), _lib.ptr(pred), _lib.ptr(gup), _lib.ptr(gp), B, Ci, Cp, H, W)
+        return None, gp, None
 
 
 def smooth_edge1(img, pred):
     """network_tools.edge_aware_smoothness_order1 (model/upflow.py:197-216) as one reduction launch + one gather backward."""
-    return SmoothEdge1Function.apply(img, pred)
+    return SmoothEdgeFunction.apply(_f32(img).contiguous(), _f32(pred).contiguous(), 1)
 
 
 # ------------------------------------------------------------------------------------------------
-# non-default loss variants (csrc/loss_variants.hip, fp32): operands must already be fp32 contiguous NCHW on the GPU
+# non-default loss variants (fp32): operands must already be fp32 contiguous NCHW on the GPU
 # ------------------------------------------------------------------------------------------------
-def _lv_check(name, *tensors):
-    for t in tensors:
-        if t is None:
-            continue
-        if t.dtype != torch.float32:
-            raise UpflowHipError('%s: float32 operands expected, got %s' % (name, t.dtype))
-    return _lib.check_gpu(*tensors)               # (GPU, contiguous, one device)
-
-
-class SmoothEdge2Function(Function):
-    @staticmethod
-    def forward(ctx, img, pred):
-        if img.dim() != 4 or pred.dim() != 4 or img.shape[0] != pred.shape[0] or img.shape[2:] != pred.shape[2:]:
-            raise UpflowHipError('smooth_edge2: img [B,Ci,H,W] and pred [B,Cp,H,W] expected, got %s / %s' % (tuple(img.shape), tuple(pred.shape)))
-        B, Ci, H, W = img.shape
-        Cp = pred.shape[1]
-        if H < 3 or W < 3:
-            raise UpflowHipError('smooth_edge2: at least 3x3 pixels')
-        dev = _lv_check('smooth_edge2', img, pred)
-        nb = _lib.lib().upf_loss_partials(B * H * W)
-        partials = torch.empty((nb, 2), dtype=torch.float32, device=img.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_smooth_edge2_forward', _lib.ptr(img), _lib.ptr(pred), _lib.ptr(partials), B, Ci, Cp, H, W, _lib.stream_ptr(dev))
-        s = partials.sum(0)
-        ctx.save_for_backward(img, pred)
-        return s[0] / float(B * Cp * (H - 2) * W) + s[1] / float(B * Cp * H * (W - 2))
-
-    @staticmethod
-    def backward(ctx, g):
-        img, pred = ctx.saved_tensors
-        B, Ci, H, W = img.shape
-        Cp = pred.shape[1]
-        gup = _f32(g).reshape(1).contiguous()
-        dev = _lib.check_gpu(img, pred, gup)
-        gp = torch.empty_like(pred)
-        with torch.cuda.device(dev):
-            _lib.call('upf_smooth_edge2_backward', _lib.ptr(img), _lib.ptr(pred), _lib.ptr(gup), _lib.ptr(gp), B, Ci, Cp, H, W, _lib.stream_ptr(dev))
-        return None, gp
-
-
 def smooth_edge2(img, pred):
     """network_tools.edge_aware_smoothness_order2 (model/upflow.py:220-243) as one reduction launch + one gather backward
     (differentiable wrt pred; the image is data)."""
-    return SmoothEdge2Function.apply(img, pred)
+    return SmoothEdgeFunction.apply(img, pred, 2)
 
 
 class SmoothDeltaFunction(Function):
@@ -1435,11 +1406,7 @@ class SmoothDeltaFunction(Function):
             raise UpflowHipError('smooth_delta: at least %dx%d pixels' % (m, m))
         dev = _lv_check('smooth_delta', flow)
         k = 6 if second_order else 2
-        nb = _lib.lib().upf_loss_partials(B * C * H * W)
-        partials = torch.empty((nb, k), dtype=torch.float32, device=flow.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_smooth_delta_forward', _lib.ptr(flow), _lib.ptr(partials), B * C, H, W, int(second_order), _lib.stream_ptr(dev))
-        s = partials.sum(0)
+        s = _partial_sums(dev, 'upf_smooth_delta_forward', B * C * H * W, k, (flow,), B * C, H, W, int(second_order))
         n = float(B * C)
         counts = [n * H * (W - 1), n * (H - 1) * W]
         if second_order:
@@ -1455,11 +1422,10 @@ class SmoothDeltaFunction(Function):
     def backward(ctx, g):
         flow, = ctx.saved_tensors
         B, C, H, W = flow.shape
-        gup = _f32(g).reshape(1).contiguous()
+        gup = _grad_scalar(g)
         dev = _lib.check_gpu(flow, gup)
         gf = torch.empty_like(flow)
-        with torch.cuda.device(dev):
-            _lib.call('upf_smooth_delta_backward', _lib.ptr(flow), _lib.ptr(gup), _lib.ptr(gf), B * C, H, W, int(ctx.second_order), _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_smooth_delta_backward', _lib.ptr(flow), _lib.ptr(gup), _lib.ptr(gf), B * C, H, W, int(ctx.second_order))
         return gf, None
 
 
@@ -1469,59 +1435,12 @@ def smooth_delta(flow, second_order=False):
     return SmoothDeltaFunction.apply(flow, second_order)
 
 
-POINTWISE_KINDS = {'charbonnier': 0, 'L1': 1}          # UPF_LOSS_CHARBONNIER, UPF_LOSS_L1 (include/upflow_hip.h)
-
-
-class PointwiseLossFunction(Function):
-    @staticmethod
-    def forward(ctx, x, y, occ, kind, q):
-        if kind not in POINTWISE_KINDS:
-            raise UpflowHipError("pointwise_loss: kind must be 'charbonnier' or 'L1', got %r" % (kind,))
-        if x.shape != y.shape or x.dim() != 4:
-            raise UpflowHipError('pointwise_loss: two [B,C,H,W] tensors expected, got %s / %s' % (tuple(x.shape), tuple(y.shape)))
-        B, C, H, W = x.shape
-        if occ is not None and tuple(occ.shape) != (B, 1, H, W):
-            raise UpflowHipError('pointwise_loss: occlusion mask must be [B,1,H,W], got %s' % (tuple(occ.shape),))
-        dev = _lv_check('pointwise_loss', x, y, occ)
-        nb = _lib.lib().upf_loss_partials(B * H * W)
-        partials = torch.empty((nb, 2), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_pointwise_loss_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(partials), B, C, H * W,
-                      POINTWISE_KINDS[kind], float(q), _lib.stream_ptr(dev))
-        sums = partials.sum(0)
-        ctx.save_for_backward(x, y, occ)
-        ctx.cfg = (POINTWISE_KINDS[kind], float(q))
-        s_loss, s_occ = sums.unbind(0)
-        ctx.mark_non_differentiable(s_occ)
-        ctx.set_materialize_grads(False)
-        return s_loss, s_occ
-
-    @staticmethod
-    def backward(ctx, g, _g_occ):
-        if g is None:
-            return None, None, None, None, None
-        if ctx.needs_input_grad[2]:
-            raise UpflowHipError('pointwise_loss: the occlusion weights are treated as constants (hard masks); a mask that '
-                                 'requires grad would silently get a zero gradient')
-        x, y, occ = ctx.saved_tensors
-        kind, q = ctx.cfg
-        B, C, H, W = x.shape
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
-        if gx is None and gy is None:
-            return None, None, None, None, None
-        coef = _f32(g).reshape(1).contiguous()
-        dev = _lib.check_gpu(x, y, coef)
-        with torch.cuda.device(dev):
-            _lib.call('upf_pointwise_loss_backward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(occ), _lib.ptr(coef), _lib.ptr(gx), _lib.ptr(gy),
-                      B, C, H * W, kind, q, _lib.stream_ptr(dev))
-        return gx, gy, None, None, None
-
-
 def pointwise_loss_sums(x, y, occ=None, kind='charbonnier', q=0.4):
     """-> (sum over [B,C,H,W] of loss(x - y) * occ, sum of occ) for the 'charbonnier' ((d^2 + 1e-6)^q) and 'L1' (|d + 1e-6|) arms of
     network_tools.photo_loss_multi_type (model/upflow.py:273-278, :284-287): ONE deterministic reduction, differentiable wrt x, y."""
-    return PointwiseLossFunction.apply(x, y, occ, kind, q)
+    if kind not in POINTWISE_KINDS:
+        raise UpflowHipError("pointwise_loss: kind must be 'charbonnier' or 'L1', got %r" % (kind,))
+    return PointwiseLossFunction.apply(x, y, occ, kind, q, 0.0)
 
 
 def _ssim_check(name, x, y, weight, c2, weight_epsilon):
@@ -1548,9 +1467,8 @@ def _ssim_backward(ctx, gmap, coef_w, coef_u):
     if (gx is None and gy is None) or (gmap is None and coef_w is None and coef_u is None):
         return None, None
     dev = _lib.check_gpu(x, y, weight, gmap, coef_w, coef_u)
-    with torch.cuda.device(dev):
-        _lib.call('upf_ssim_backward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(gmap), _lib.ptr(coef_w), _lib.ptr(coef_u),
-                  _lib.ptr(gx), _lib.ptr(gy), B, C, H, W, c2, eps, _lib.stream_ptr(dev))
+    _lib.launch(dev, 'upf_ssim_backward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(gmap), _lib.ptr(coef_w), _lib.ptr(coef_u),
+                _lib.ptr(gx), _lib.ptr(gy), B, C, H, W, c2, eps)
     return gx, gy
 
 
@@ -1561,9 +1479,8 @@ class WeightedSsimFunction(Function):
         B, C, H, W = x.shape
         out = torch.empty((B, C, H - 2, W - 2), dtype=torch.float32, device=x.device)
         w_avg = torch.empty((B, 1, H - 2, W - 2), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_ssim_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(out), _lib.ptr(w_avg), _lib.ptr(None),
-                      B, C, H, W, float(c2), float(weight_epsilon), _lib.stream_ptr(dev))
+        _lib.launch(dev, 'upf_ssim_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(out), _lib.ptr(w_avg), _lib.ptr(None),
+                    B, C, H, W, float(c2), float(weight_epsilon))
         ctx.save_for_backward(x, y, weight)
         ctx.cfg = (float(c2), float(weight_epsilon))
         ctx.mark_non_differentiable(w_avg)
@@ -1588,12 +1505,8 @@ class SsimLossSumsFunction(Function):
     def forward(ctx, x, y, weight, c2, weight_epsilon):
         dev = _ssim_check('ssim_loss_sums', x, y, weight, c2, weight_epsilon)
         B, C, H, W = x.shape
-        nb = _lib.lib().upf_loss_partials(B * (H - 2) * (W - 2))
-        partials = torch.empty((nb, 3), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(dev):
-            _lib.call('upf_ssim_forward', _lib.ptr(x), _lib.ptr(y), _lib.ptr(weight), _lib.ptr(None), _lib.ptr(None), _lib.ptr(partials),
-                      B, C, H, W, float(c2), float(weight_epsilon), _lib.stream_ptr(dev))
-        s_lw, s_w, s_l = partials.sum(0).unbind(0)
+        s_lw, s_w, s_l = _partial_sums(dev, 'upf_ssim_forward', B * (H - 2) * (W - 2), 3, (x, y, weight, None, None),
+                                       B, C, H, W, float(c2), float(weight_epsilon)).unbind(0)
         ctx.save_for_backward(x, y, weight)
         ctx.cfg = (float(c2), float(weight_epsilon))
         ctx.mark_non_differentiable(s_w)
@@ -1602,8 +1515,8 @@ class SsimLossSumsFunction(Function):
 
     @staticmethod
     def backward(ctx, g_lw, _g_w, g_l):
-        coef_w = None if g_lw is None else _f32(g_lw).reshape(1).contiguous()
-        coef_u = None if g_l is None else _f32(g_l).reshape(1).contiguous()
+        coef_w = None if g_lw is None else _grad_scalar(g_lw)
+        coef_u = None if g_l is None else _grad_scalar(g_l)
         gx, gy = _ssim_backward(ctx, None, coef_w, coef_u)
         return gx, gy, None, None, None
 
