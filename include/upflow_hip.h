@@ -187,7 +187,10 @@ int upf_warp_forward_strided(const void* x, long long x_batch_stride, const floa
                              int B, int C, int H, int W, int dtype, int mask_mode, int batch_shift, void* stream);
 /* same with PITCHED rows (round 5): rows of x / y are x_row_pitch / y_row_pitch elements apart (>= W, 0 = W; plane stride H * pitch,
  * batch strides 0 = C * H * pitch); the flow stays a contiguous fp32 tensor.  With an even y pitch odd-width levels keep the 4-byte
- * (two-pixel) stores — the pixel beyond W lands in the row's own padding.  Same values as the contiguous forms. */
+ * (two-pixel) stores — the pixel beyond W lands in the row's own padding.  Same values as the contiguous forms.
+ * Batch strides: at least C * H * pitch - (pitch - W), i.e. the padding of an image's last row need not exist.  A y_batch_stride of
+ * C * H * pitch or more (or 0) PROMISES that every row of every image, the last included, owns its full pitch: only then is
+ * column W of an odd-width row written (with an unspecified value); below that nothing outside the [.., :W] view is touched. */
 int upf_warp_forward_pitched(const void* x, long long x_batch_stride, int x_row_pitch, const float* flow, void* y, long long y_batch_stride,
                              int y_row_pitch, int B, int C, int H, int W, int dtype, int mask_mode, int batch_shift, void* stream);
 /* same on CHANNEL-OCTET tensors ("C8": [n][C/8][H][W][8], see upf_conv_forward_c8; bf16 / fp16): x8 / y8 point at the first

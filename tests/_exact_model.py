@@ -1,7 +1,9 @@
 """Exactly representable operands for the 16-bit convolution kernels (csrc/conv3x3.hip, conv_kernel.hpp, conv_c8.hip, conv_pair.hip,
 conv_wgrad.hip), their fp64 reference, the guard that makes bit equality a fair demand, and the NaN arena the operands live in.
 Shared by tests/test_hip_conv_exact.py (GPU) and tests/test_exact_model_cpu.py (the conditions, no GPU).  Plain torch, no GPU import.
-The last section does the same for the cost-volume kernels (csrc/corr81_*.hip; tests/test_hip_corr_exact.py).
+The cost-volume section does the same for csrc/corr81_*.hip (tests/test_hip_corr_exact.py); the last section models the sampling
+kernels — backward warp and flow resize — whose weights come out of an fp32 position chain (tests/test_hip_warp_exact.py,
+tests/test_hip_resize_exact.py).
 
 The idea: every operand sits on a grid (an integer multiple of a power of two, few significant bits).  Every product is then a
 multiple of the QUANTUM (the product of the two grid steps) and so is every partial sum, in any order.  If the sum of the ABSOLUTE
@@ -16,6 +18,7 @@ y = pre > 0 ? pre : slope * pre.  The exact matrix uses slope 0.125 (a power of 
 import functools
 import zlib
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -742,3 +745,520 @@ def corr_nonfinite_bwd(shape, dtype, kind):
     guard_corr_grads(f1, f2, go, dtype, CORR_GRIDS[dtype]['g'][0])
     inside = 0 <= y + dy < H and 0 <= x + dx < W
     return (f1, f2, go) + tuple(corr_grad_sums(f1, f2, go)) + (C, C if inside else 0)
+
+
+# ---- sampling: the backward warp (csrc/warp.hip, sampling.hpp) and the flow resize (csrc/sgu_blend.hip upsample_*) -------------------
+# Shared by tests/test_hip_warp_exact.py, tests/test_hip_resize_exact.py (GPU) and tests/test_exact_model_cpu.py.  numpy on the CPU.
+#
+# csrc/sampling.hpp calls its position chain a bit-exact contract (every step a separately rounded fp32 operation in a fixed
+# order): `taps32` / `lerp32` restate it in np.float32, one numpy operation per rounded step.  What is NOT part of the contract is
+# the association of the four-tap sum, so a value is compared in one of two regimes:
+#   dyadic    H-1, W-1 powers of two (or H, W of 1 or 2), flows multiples of 1/8, data on the per-dtype grids: positions, weights
+#             (multiples of 1/64), every product and every partial sum are exact in fp32 in any order; the expected value is the plain
+#             fp64 bilinear formula rounded ONCE to the storage type (`sampling_guard` checks the conditions).
+#   general   any size, any fp32 flow: the weights are taps32's fp32 values, the value their fp64 dot product with the taps, accepted
+#             within the standard bound of the fp32 evaluation (gamma_n = n u / (1 - n u), u = 2^-24), computed per element.
+# The scattered data gradient is fully specified in both regimes (csrc/common.hpp fix_q / fix_get): integers, so bit for bit.
+F32 = torch.float32
+U32 = 2.0 ** -24
+FIX = 2.0 ** 44
+MODES = ('none', 'literal', 'robust')
+MODE_CODES = {'none': 0, 'literal': 1, 'robust': 2}
+SAMP_DTYPES = (torch.bfloat16, torch.float16, F32)
+SAMP_NAMES = {torch.bfloat16: 'bf16', torch.float16: 'fp16', F32: 'fp32'}
+SAMP_GRID = {torch.bfloat16: torch.bfloat16, torch.float16: torch.float16, F32: torch.float16}      # fp32 runs on the fp16 grids
+FLOW_STEP = 0.125
+
+
+def gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+def rne(v64, dtype):
+    """ONE round-to-nearest-even of an fp64 array to `dtype` (a torch tensor of that dtype).  Not through fp32: torch converts fp64
+    to a 16-bit type in two roundings.  fp16 / fp32: numpy's direct conversions; bf16: 8 significant bits by frexp / rint (the
+    values here are far from bf16's subnormal and overflow ranges)."""
+    v = np.asarray(v64, dtype=np.float64)
+    if dtype == F32:
+        return torch.from_numpy(v.astype(np.float32))
+    if dtype == torch.float16:
+        return torch.from_numpy(v.astype(np.float16))
+    m, e = np.frexp(v)
+    r = np.ldexp(np.rint(m * 256.0), e - 8)
+    assert np.all(np.abs(r[np.isfinite(r)]) < 2.0 ** 100)
+    return torch.from_numpy(r.astype(np.float32)).to(torch.bfloat16)
+
+
+def taps32(flow, H, W):
+    """make_taps / taps_valid of csrc/sampling.hpp, step by step in np.float32.  flow: [B,2,H,W] fp32.
+    -> dict: ix, iy, ax, bx, ay, by, w (4 x [B,H,W], nw ne sw se) as np.float32; x0, y0 int64 (clamped to [-2, size+1], NaN -> -2);
+    inb (4 x bool); valid {'none', 'literal', 'robust'} bool."""
+    f = np.ascontiguousarray(np.asarray(flow, dtype=np.float32))
+    assert f.shape[1:] == (2, H, W)
+    one, two, zero = np.float32(1), np.float32(2), np.float32(0)
+    jj = np.arange(W, dtype=np.float32)[None, None, :]
+    ii = np.arange(H, dtype=np.float32)[None, :, None]
+    with np.errstate(all='ignore'):
+        px, py = jj + f[:, 0], ii + f[:, 1]
+        gx = (two * px) / np.float32(max(W - 1, 1)) - one
+        gy = (two * py) / np.float32(max(H - 1, 1)) - one
+        ix = ((gx + one) / two) * np.float32(W - 1)
+        iy = ((gy + one) / two) * np.float32(H - 1)
+        fx0, fy0 = np.floor(ix), np.floor(iy)
+        fx1, fy1 = fx0 + one, fy0 + one
+        ax, bx, ay, by = fx1 - ix, ix - fx0, fy1 - iy, iy - fy0
+        w = [ax * ay, bx * ay, ax * by, bx * by]
+        x0 = np.where(np.isnan(fx0), -2.0, np.clip(fx0, -2.0, W + 1.0)).astype(np.int64)
+        y0 = np.where(np.isnan(fy0), -2.0, np.clip(fy0, -2.0, H + 1.0)).astype(np.int64)
+        xin = [(x0 >= 0) & (x0 <= W - 1), (x0 + 1 >= 0) & (x0 + 1 <= W - 1)]
+        yin = [(y0 >= 0) & (y0 <= H - 1), (y0 + 1 >= 0) & (y0 + 1 <= H - 1)]
+        inb = [xin[0] & yin[0], xin[1] & yin[0], xin[0] & yin[1], xin[1] & yin[1]]
+        s = np.where(inb[0], w[0], zero)
+        for k in (1, 2, 3):
+            s = s + np.where(inb[k], w[k], zero)
+        assert s.dtype == np.float32 and ix.dtype == np.float32
+        valid = {'none': np.ones(px.shape, dtype=bool), 'literal': s >= one,
+                 'robust': (px >= zero) & (px <= np.float32(W - 1)) & (py >= zero) & (py <= np.float32(H - 1))}
+    return dict(ix=ix, iy=iy, ax=ax, bx=bx, ay=ay, by=by, w=w, x0=x0, y0=y0, inb=inb, valid=valid, px=px, py=py)
+
+
+def taps64(flow, H, W):
+    """The plain fp64 bilinear taps at (j + fx, i + fy) (a size of 1 pins that coordinate to 0, as the normalisation by
+    max(size - 1, 1) followed by the multiplication with size - 1 does): the dyadic regime's reference, same keys as taps32."""
+    f = np.asarray(flow, dtype=np.float64)
+    px = np.arange(W, dtype=np.float64)[None, None, :] + f[:, 0]
+    py = np.arange(H, dtype=np.float64)[None, :, None] + f[:, 1]
+    with np.errstate(all='ignore'):
+        ix = px if W > 1 else px * 0.0
+        iy = py if H > 1 else py * 0.0
+        fx0, fy0 = np.floor(ix), np.floor(iy)
+        ax, bx, ay, by = fx0 + 1 - ix, ix - fx0, fy0 + 1 - iy, iy - fy0
+        w = [ax * ay, bx * ay, ax * by, bx * by]
+        x0 = np.where(np.isnan(fx0), -2.0, np.clip(fx0, -2.0, W + 1.0)).astype(np.int64)
+        y0 = np.where(np.isnan(fy0), -2.0, np.clip(fy0, -2.0, H + 1.0)).astype(np.int64)
+        xin = [(x0 >= 0) & (x0 <= W - 1), (x0 + 1 >= 0) & (x0 + 1 <= W - 1)]
+        yin = [(y0 >= 0) & (y0 <= H - 1), (y0 + 1 >= 0) & (y0 + 1 <= H - 1)]
+        inb = [xin[0] & yin[0], xin[1] & yin[0], xin[0] & yin[1], xin[1] & yin[1]]
+        s = sum(np.where(inb[k], w[k], 0.0) for k in range(4))
+        valid = {'none': np.ones(px.shape, dtype=bool), 'literal': s >= 1.0,
+                 'robust': (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)}
+    return dict(ix=ix, iy=iy, ax=ax, bx=bx, ay=ay, by=by, w=w, x0=x0, y0=y0, inb=inb, valid=valid, px=px, py=py)
+
+
+def _tap_index(t, k, H, W):
+    return np.clip(t['y0'] + (k >> 1), 0, H - 1), np.clip(t['x0'] + (k & 1), 0, W - 1)
+
+
+def _tap_weight(t, k):
+    return np.where(t['inb'][k], t['w'][k].astype(np.float64), 0.0)        # (a NaN weight of an outside tap is NOT multiplied)
+
+
+def warp_forward_ref(x, t, mode, shift=0):
+    """x [B,C,H,W] (any float array; used as fp64), t = taps32 / taps64 of the flow.  -> (y fp64, sum |w_k v_k| fp64), both zero
+    where the mask of `mode` rejects the pixel; output item n samples x[(n + shift) % B]."""
+    x = np.asarray(x, dtype=np.float64)
+    B, C, H, W = x.shape
+    xs = np.roll(x, -shift, axis=0)
+    n = np.arange(B)[:, None, None]
+    y, ya = np.zeros_like(x), np.zeros_like(x)
+    for k in range(4):
+        yk, xk = _tap_index(t, k, H, W)
+        v = np.moveaxis(xs[n, :, yk, xk], -1, 1) * _tap_weight(t, k)[:, None]
+        y += v
+        ya += np.abs(v)
+    m = t['valid'][mode][:, None]
+    return np.where(m, y, 0.0), np.where(m, ya, 0.0)
+
+
+def warp_gx_model(gy, t, mode, shift, dtype):
+    """The data gradient bit for bit (csrc/warp.hip warp_bwd_kernel, csrc/common.hpp fix_q / fix_get): per in-bounds tap of a
+    valid pixel rint(fp32(w_k * g) * 2^44) as an integer from ONE fp32 multiply, summed as integers into the source image
+    (n + shift) % B, then fp32(double(q) * 2^-44), then RNE to `dtype`.  gy: [B,C,H,W] values representable in `dtype`;
+    t = taps32.  -> (gx tensor of `dtype`, the integer sums)."""
+    g32 = np.asarray(gy, dtype=np.float32)
+    B, C, H, W = g32.shape
+    q = np.zeros((B, C, H * W), dtype=np.int64)
+    n = np.arange(B)[:, None, None]
+    ns = np.broadcast_to((n + shift) % B, t['x0'].shape)
+    for k in range(4):
+        on = t['inb'][k] & t['valid'][mode]
+        yk, xk = _tap_index(t, k, H, W)
+        with np.errstate(all='ignore'):
+            prod = (t['w'][k][:, None] * g32).astype(np.float32)                       # one fp32 multiply
+        s = prod.astype(np.float64) * FIX
+        assert np.all(np.abs(s[np.broadcast_to(on[:, None], s.shape)]) < 2.0 ** 59)
+        c = np.rint(np.where(on[:, None], s, 0.0)).astype(np.int64)
+        for ch in range(C):
+            np.add.at(q, (ns[on], ch, (yk * W + xk)[on]), c[:, ch][on])
+    assert np.all(np.abs(q) < 2 ** 53)
+    v32 = (q.astype(np.float64) * (1.0 / FIX)).astype(np.float32).reshape(B, C, H, W)
+    return rne(v32.astype(np.float64), dtype), q.reshape(B, C, H, W)
+
+
+def warp_backward_ref(x, gy, t, mode, shift=0):
+    """fp64: -> (gx, gflow, sum |terms| of gflow).  gx[(n + shift) % B, c, tap] += w_k * gy; gflow_x = sum_c gy * (ay * (ne - nw) +
+    by * (se - sw)), gflow_y = sum_c gy * (ax * (sw - nw) + bx * (se - ne)) over the in-bounds taps — the position's derivative with
+    respect to the flow is 1 (0 for a size of 1: that coordinate is pinned) —, all zero where the mask rejects the pixel."""
+    x, gy = np.asarray(x, dtype=np.float64), np.asarray(gy, dtype=np.float64)
+    B, C, H, W = x.shape
+    xs = np.roll(x, -shift, axis=0)
+    n = np.arange(B)[:, None, None]
+    ns = np.broadcast_to((n + shift) % B, t['x0'].shape)
+    m = t['valid'][mode]
+    gx = np.zeros((B, C, H * W))
+    gf, gfa = np.zeros((B, 2, H, W)), np.zeros((B, 2, H, W))
+    d = {k: t[k].astype(np.float64) for k in ('ax', 'bx', 'ay', 'by')}
+    fac = [(-d['ay'], -d['ax']), (d['ay'], -d['bx']), (-d['by'], d['ax']), (d['by'], d['bx'])]
+    for k in range(4):
+        on = t['inb'][k] & m
+        yk, xk = _tap_index(t, k, H, W)
+        wk = _tap_weight(t, k)
+        for ch in range(C):
+            np.add.at(gx, (ns[on], ch, (yk * W + xk)[on]), (wk * gy[:, ch])[on])
+        v = np.moveaxis(xs[n, :, yk, xk], -1, 1)
+        for comp in (0, 1):
+            with np.errstate(all='ignore'):
+                term = np.where(on[:, None], v * fac[k][comp][:, None] * gy, 0.0)
+            gf[:, comp] += term.sum(1)
+            gfa[:, comp] += np.abs(term).sum(1)
+    for comp, size in ((0, W), (1, H)):
+        if size == 1:
+            gf[:, comp] = 0.0
+            gfa[:, comp] = 0.0
+    return gx.reshape(B, C, H, W), gf, gfa
+
+
+def warp_counts(t, mode, shift, B, H, W):
+    """What a backward case claims, counted on the model: merged lane pairs (warp_bwd_kernel's m1 / m3: lanes p, p + 1 of one wave
+    whose right-hand / left-hand taps share an address), source pixels that receive contributions of >= 2 output pixels, taps
+    outside the image, pixels the mask rejects."""
+    m = t['valid'][mode].reshape(B, -1)
+    inb = [(t['inb'][k].reshape(B, -1) & m) for k in range(4)]
+    o = [(lambda yx: yx[0] * W + yx[1])(_tap_index(t, k, H, W)).reshape(B, -1) for k in range(4)]
+    lane = np.arange(H * W) & 63
+    merged = 0
+    for r, l in ((1, 0), (3, 2)):
+        merged += int((inb[r][:, :-1] & inb[l][:, 1:] & (o[r][:, :-1] == o[l][:, 1:]) & (lane[:-1] < 63)).sum())
+    hits = np.zeros((B, H * W), dtype=np.int64)
+    nn = np.broadcast_to(((np.arange(B)[:, None] + shift) % B), m.shape)
+    for k in range(4):
+        np.add.at(hits, (nn[inb[k]], o[k][inb[k]]), 1)
+    outside = sum(int((~t['inb'][k].reshape(B, -1) & m).sum()) for k in range(4))
+    return dict(merged=merged, collisions=int((hits >= 2).sum()), outside=outside, invalid=int((~m).sum()))
+
+
+# cases: (B, C, H, W).  Dyadic sizes; (1,32,9,65) splits its channels over blockIdx.y, (1,33,9,65) with a short last slice; W == 1 is
+# the narrow kernel.  General sizes: odd and even rows, (2,2,64,512) the smallest grid that takes four pixels per thread (fp32 only).
+WARP_DYADIC = [(1, 1, 1, 1), (1, 3, 5, 9), (2, 5, 17, 33), (1, 32, 9, 65), (1, 33, 9, 65), (1, 3, 9, 1), (2, 4, 1, 9), (1, 2, 3, 2)]
+WARP_GENERAL = [(1, 7, 6, 20), (2, 16, 13, 26), (1, 3, 12, 40), (1, 5, 7, 13)]
+WARP_PXT4 = (2, 2, 64, 512)
+WARP_BWD_GENERAL = WARP_GENERAL[:3]
+WARP_C8_DYADIC = [(2, 8, 5, 9), (1, 32, 5, 9), (2, 40, 5, 9)]             # 1, 4 and 5 octets
+WARP_C8_GENERAL = [(1, 40, 6, 20)]
+FWD_PATTERNS = ('const', 'int', 'rand4', 'edges', 'nonfinite')
+BWD_PATTERNS = ('const', 'converge', 'rand4', 'nonfinite')
+NONFINITE = (float('nan'), float('inf'), -1e30)
+
+
+def is_dyadic_size(n):
+    return n in (1, 2) or (n - 1) & (n - 2) == 0
+
+
+def nonfinite_places(B, H, W):
+    """[(n, component, i, j)] of the three non-finite flow values (NaN, +inf, -1e30): spread over the image."""
+    HW = H * W
+    ps = [HW // 4, HW // 2, (3 * HW) // 4] if HW >= 3 else [0] * 3
+    return [(B - 1 if k else 0, k % 2, p // W, p % W) for k, p in enumerate(ps)]
+
+
+def warp_flow(shape, pattern, dyadic):
+    """-> flow [B,2,H,W] np.float32.  Dyadic: multiples of 1/8 with |f| <= 10.
+    const: one fractional displacement (neighbouring lanes sample neighbouring source pixels: the lane merge is active across lanes
+    63 / 64 and across row ends); int: integers; rand4: random, up to 4 pixels (taps outside on every side); edges: positions
+    exactly on -1, 0, W-1, H-1 (general: and one fp32 step either side); converge: every pixel of the top rows lands on ONE source
+    position; nonfinite: rand4 with a NaN, a +inf and a -1e30."""
+    B, _, H, W = shape
+    rng = np.random.RandomState(seed_of('warpflow', tuple(shape), pattern, dyadic) % (2 ** 31))
+    jj = np.broadcast_to(np.arange(W, dtype=np.float64)[None, None, :], (B, H, W))
+    ii = np.broadcast_to(np.arange(H, dtype=np.float64)[None, :, None], (B, H, W))
+    f = np.zeros((B, 2, H, W))
+    q = (lambda v: np.round(v / FLOW_STEP) * FLOW_STEP) if dyadic else (lambda v: v)
+    if pattern == 'const':
+        f[:, 0], f[:, 1] = (0.375, -0.25) if dyadic else (0.3, -0.7)
+    elif pattern == 'int':
+        f[:] = rng.randint(-2, 3, f.shape)
+    elif pattern in ('rand4', 'nonfinite'):
+        f[:] = q(rng.uniform(-4, 4, f.shape))
+    elif pattern == 'edges':
+        tx = rng.choice([-1.0, 0.0, W - 1.0, float(W)], (B, H, W))
+        ty = rng.choice([-1.0, 0.0, H - 1.0, float(H)], (B, H, W))
+        keep = rng.rand(B, H, W) < 0.5                           # half the pixels pin x, the others y; the free coordinate stays inside
+        f[:, 0] = np.where(keep, tx - jj, q(rng.uniform(-0.9, 0.9, (B, H, W))))
+        f[:, 1] = np.where(keep, q(rng.uniform(-0.9, 0.9, (B, H, W))), ty - ii)
+        f = np.clip(f, -10, 10)
+        f32 = f.astype(np.float32)
+        if not dyadic:
+            step = rng.randint(-1, 2, f.shape)
+            f32 = np.where(step > 0, np.nextafter(f32, np.float32(np.inf)), np.where(step < 0, np.nextafter(f32, np.float32(-np.inf)), f32))
+        return f32.astype(np.float32)
+    elif pattern == 'converge':
+        top = ii < max(1, H // 2)
+        f[:, 0] = np.where(top, (W - 1) // 2 + (0.5 if W > 2 else 0.0) - jj, q(rng.uniform(-1, 1, (B, H, W))))
+        f[:, 1] = np.where(top, (H - 1) // 2 + (0.25 if H > 2 else 0.0) - ii, q(rng.uniform(-1, 1, (B, H, W))))
+        f = np.clip(f, -10, 10)
+    else:
+        raise KeyError(pattern)
+    f = f.astype(np.float32)
+    if pattern == 'nonfinite':
+        for (n, c, i, j), v in zip(nonfinite_places(B, H, W), NONFINITE):
+            f[n, c, i, j] = v
+    return f
+
+
+def sampling_guard(x, gy, flow, t32, dtype):
+    """The dyadic regime's conditions, from the operands and the model alone: dyadic sizes; finite flows multiples of 1/8 within
+    +-10; taps32's position equals j + fx (0 for a size of 1) and its weights are multiples of 1/64; x and grad_y on their grids.
+    Then every product w * v (quantum step_x / 64), w * g, v * a * g (quantum step_x * step_g / 8) and every partial sum is an
+    integer number of quanta far below 2^24 (at most 4 C terms of bounded size: checked)."""
+    B, C, H, W = x.shape
+    G = GRIDS[SAMP_GRID[dtype]]
+    assert is_dyadic_size(H) and is_dyadic_size(W), (H, W)
+    f = np.asarray(flow, dtype=np.float64)
+    fin = np.isfinite(f) & (np.abs(f) < 1e29)                      # (NONFINITE holds a -1e30: out of every range, like inf)
+    assert np.all(np.abs(f[fin]) <= 10.0) and np.all(f[fin] / FLOW_STEP == np.round(f[fin] / FLOW_STEP))
+    t64 = taps64(flow, H, W)
+    ok = fin[:, 0] & fin[:, 1]
+    for k in ('ix', 'iy', 'ax', 'bx', 'ay', 'by'):
+        assert np.array_equal(t32[k][ok].astype(np.float64), t64[k][ok]), k
+    for k in range(4):
+        wk = t32['w'][k][ok].astype(np.float64)
+        assert np.array_equal(wk, t64['w'][k][ok]) and np.all(wk * 64 == np.round(wk * 64))
+        assert np.array_equal(t32['inb'][k], t64['inb'][k])
+    for mode in MODES:
+        assert np.array_equal(t32['valid'][mode], t64['valid'][mode]), mode
+    assert np.array_equal(t32['x0'], t64['x0']) and np.array_equal(t32['y0'], t64['y0'])
+    xt, gt = torch.as_tensor(np.asarray(x)), torch.as_tensor(np.asarray(gy))
+    assert on_grid(xt, G['x'][0]) and on_grid(gt, G['gy'][0])
+    top = 4 * C * G['x'][1] * G['gy'][1] / (G['x'][0] * G['gy'][0] / 8 / 64)
+    assert top < LIMIT, top
+    return top
+
+
+@functools.lru_cache(maxsize=None)
+def warp_case(shape, dtype, pattern, dyadic):
+    """-> dict x, gy (np.float32, representable in `dtype`), flow (np.float32), t (taps32), dyadic.  Computed once, shared, never
+    written to.  Dyadic: data on the grids of GRIDS (fp32 on the fp16 ones); general: normal deviates rounded to `dtype`."""
+    B, C, H, W = shape
+    gen = torch.Generator().manual_seed(seed_of('warp', tuple(shape), SAMP_NAMES[dtype], pattern))
+    if dyadic:
+        G = GRIDS[SAMP_GRID[dtype]]
+        x, gy = grid(shape, G['x'][0], G['x'][1], gen), grid(shape, G['gy'][0], G['gy'][1], gen)
+    else:
+        x, gy = (torch.randn(shape, generator=gen).to(dtype).float() for _ in range(2))
+    flow = warp_flow((B, 2, H, W), pattern, dyadic)
+    t = taps32(flow, H, W)
+    c = dict(x=x.numpy(), gy=gy.numpy(), flow=flow, t=t, dyadic=dyadic, shape=shape)
+    if dyadic:
+        sampling_guard(c['x'], c['gy'], flow, t, dtype)
+    return c
+
+
+def y_candidates(ref, bound, dtype):
+    """-> (lo, hi) tensors of `dtype`: RNE(ref - bound), RNE(ref + bound)."""
+    return rne(ref - bound, dtype), rne(ref + bound, dtype)
+
+
+def accept_y(got, ref, bound, dtype):
+    """-> bool array: the general regime's rule for y (bound = gamma_4 * sum |w_k v_k|; 0 in the dyadic regime).  fp32: got lies in
+    [ref - bound, ref + bound] (evaluated in fp64); 16-bit: got equals RNE(ref - bound) or RNE(ref + bound) — or, where cancellation
+    leaves a result so small that the interval spans more than two 16-bit values (fp16 near 2^-12: one ulp is 2^-22, the bound of
+    four terms of size 1/4 is as much), a 16-bit value between the two: rounding is monotone, so these are exactly the roundings of
+    the fp32 values the interval holds.  (The two ends differ for <= 1 % of the elements: tests/test_exact_model_cpu.py.)"""
+    g = got.detach().cpu()
+    assert g.dtype == dtype
+    if dtype == F32:
+        g64 = g.double().numpy()
+        return (g64 >= ref - bound) & (g64 <= ref + bound)
+    lo, hi = y_candidates(ref, bound, dtype)
+    return ((g.float() >= lo.float()) & (g.float() <= hi.float())).numpy()
+
+
+def two_candidate_share(ref, bound, dtype):
+    lo, hi = y_candidates(ref, bound, dtype)
+    return float((lo != hi).float().mean())
+
+
+def warp_pxt(dtype, B, C, H, W, y_pitch=0, y_align=16, y_batch_stride=0):
+    """upf_warp_forward_pitched's choice, read off the host code: 'narrow' (W < 2), else pixels per thread 'pxt4' / 'pxt2' / 'pxt1'.
+    y_align: the largest power of two (bytes, up to 16) that divides y's address; pitch / batch stride 0 = W / C * H * pitch.  A pair
+    store at an odd W lands its second pixel in the row's pitch padding, so it is taken only where the batch stride promises the
+    full pitch behind every row (>= C * H * pitch)."""
+    if W < 2:
+        return 'narrow'
+    yp = y_pitch or W
+    ybs = y_batch_stride or C * H * yp
+    if dtype == F32 and yp % 4 == 0 and W % 4 == 0 and y_align >= 16 and ybs % 4 == 0 and B * H * W >= 4 * 64 * 256:
+        return 'pxt4'
+    if dtype != F32 and yp % 2 == 0 and y_align >= 4 and ybs % 2 == 0 and (W % 2 == 0 or ybs >= C * H * yp):
+        return 'pxt2'
+    return 'pxt1'
+
+
+def pick_cpt(B, C, groups, threads=256):
+    """csrc/warp.hip pick_cpt -> (channels per thread, channel slices)."""
+    blocks = B * ((groups + threads - 1) // threads)
+    split = 1
+    while split < C and blocks * split < 1024 and C // (split * 2) >= 8:
+        split *= 2
+    cpt = (C + split - 1) // split
+    return cpt, (C + cpt - 1) // cpt
+
+
+# ---- the flow resize ------------------------------------------------------------------------------------------------------------------
+RESIZE_GRID = (0.25, 4.0)
+RESIZE_FWD_DYADIC = [((5, 9), (9, 17)), ((3, 5), (9, 17)), ((9, 17), (5, 9)), ((3, 5), (3, 5)), ((1, 1), (9, 16)), ((2, 3), (1, 1))]
+RESIZE_FWD_GENERAL = [((4, 13), (16, 52)), ((6, 20), (12, 40)), ((5, 7), (11, 6))]
+# backward: route (upsample_bwd_route) -> dyadic cases; the smallest shapes that reach each
+RESIZE_BWD_ROUTES = [('group1', ((3, 5), (3, 5))), ('group1', ((9, 17), (5, 9))), ('group4', ((5, 9), (9, 17))), ('group16', ((3, 1), (17, 9))),
+                     ('group16_notable', ((5, 1), (5, 40))), ('wg', ((3, 1), (33, 33))), ('wg_notable', ((2, 1), (257, 9))),
+                     ('wg_notable', ((1, 1), (9, 257))), ('band', ((5, 9), (65, 129))), ('band_2bands', ((3, 33), (9, 513))),
+                     ('band_norowtable', ((2, 2), (1025, 3))), ('group16', ((5, 9), (129, 1)))]      # (the last: W == 1)
+RESIZE_BWD_GENERAL = [((4, 13), (64, 208)), ((5, 7), (11, 6))]
+RESIZE_BC = (2, 6)                                     # B * C: [1, 2, ...] and [3, 2, ...]
+RESIZE_TREE_DEPTH = 8                                  # the deepest fixed-order tree of the five kernels: 256 -> 1 in LDS
+
+
+def lerp32(n_out, n_in):
+    """make_lerp of csrc/sampling.hpp for dst = 0 .. n_out-1 in np.float32: scale by IEEE division ((in-1)/(out-1), 0 for out <= 1),
+    src = scale * dst, truncation, l1 = src - i0, l0 = 1 - l1.  -> i0, i1 (int64), l0, l1 (np.float32)."""
+    one = np.float32(1)
+    scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0)
+    src = scale * np.arange(n_out, dtype=np.float32)
+    i0 = np.minimum(src.astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    l1 = src - i0.astype(np.float32)
+    l0 = one - l1
+    assert l0.dtype == np.float32 and l1.dtype == np.float32
+    return i0, i1, l0, l1
+
+
+def lerp_matrix(n_out, n_in):
+    """[n_out, n_in] fp64: row i holds upsample_bwd_weight(make_lerp(i), a) = (i0 == a ? l0 : 0) + (i1 == a ? l1 : 0), the sum taken
+    in fp32 like the kernels take it (both taps fall on the last input where the source index is clamped)."""
+    i0, i1, l0, l1 = lerp32(n_out, n_in)
+    a = np.arange(n_in)[None, :]
+    m = np.where(i0[:, None] == a, l0[:, None], np.float32(0)) + np.where(i1[:, None] == a, l1[:, None], np.float32(0))
+    assert m.dtype == np.float32
+    return m.astype(np.float64)
+
+
+def resize_rates(h, w, H, W):
+    """(rate of channel 0, of channel 1) = fp32(W / w), fp32(H / h)."""
+    return float(np.float32(W / w)), float(np.float32(H / h))
+
+
+def resize_forward_ref(x, H, W, if_rate):
+    """x [B,C,h,w] -> (y fp64, sum of |terms| fp64): l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d) in fp64 with lerp32's fp32
+    weights; if_rate (C == 2): times fp32(W / w) / fp32(H / h)."""
+    x = np.asarray(x, dtype=np.float64)
+    B, C, h, w = x.shape
+    yi0, yi1, yl0, yl1 = lerp32(H, h)
+    xi0, xi1, xl0, xl1 = lerp32(W, w)
+    yl0, yl1 = yl0.astype(np.float64)[:, None], yl1.astype(np.float64)[:, None]
+    xl0, xl1 = xl0.astype(np.float64)[None, :], xl1.astype(np.float64)[None, :]
+    a, b = x[:, :, yi0][:, :, :, xi0], x[:, :, yi0][:, :, :, xi1]
+    c, d = x[:, :, yi1][:, :, :, xi0], x[:, :, yi1][:, :, :, xi1]
+    y = yl0 * (xl0 * a + xl1 * b) + yl1 * (xl0 * c + xl1 * d)
+    ya = np.abs(yl0) * (np.abs(xl0 * a) + np.abs(xl1 * b)) + np.abs(yl1) * (np.abs(xl0 * c) + np.abs(xl1 * d))
+    if if_rate:
+        r = np.array(resize_rates(h, w, H, W)).reshape(1, 2, 1, 1)
+        y, ya = y * r, ya * r
+    return y, ya
+
+
+def resize_backward_ref(gy, h, w, if_rate):
+    """The exact adjoint: gx[a, b] = sum_ij gy[i, j] * wy(i, a) * wx(j, b) in fp64 (times the rate).  -> (gx, sum of |terms|, number
+    of non-zero weights of each input pixel's footprint)."""
+    gy = np.asarray(gy, dtype=np.float64)
+    B, C, H, W = gy.shape
+    My, Mx = lerp_matrix(H, h), lerp_matrix(W, w)
+    gx = np.einsum('ia,ncij,jb->ncab', My, gy, Mx)
+    ga = np.einsum('ia,ncij,jb->ncab', np.abs(My), np.abs(gy), np.abs(Mx))
+    nnz = (My != 0).sum(0)[:, None] * (Mx != 0).sum(0)[None, :]
+    if if_rate:
+        r = np.array(resize_rates(h, w, H, W)).reshape(1, 2, 1, 1)
+        gx, ga = gx * r, ga * r
+    return gx, ga, nnz
+
+
+def is_dyadic_ratio(n_in, n_out):
+    if n_out <= 1 or n_in == 1:
+        return True
+    r = (n_in - 1) / (n_out - 1)
+    m, _ = np.frexp(r)
+    return m == 0.5
+
+
+def resize_guard(data, h, w, H, W):
+    """Dyadic resize: (in-1)/(out-1) a power of two or 0, data multiples of 1/4 within +-4.  The weights are then multiples of the
+    ratio (or of 1), every product gy * wy * wx a multiple of the quantum, and the sum of the absolute terms of any output stays
+    below 2^24 quanta: exact in fp32 in any order and any grouping.  -> that maximum in quanta."""
+    assert is_dyadic_ratio(h, H) and is_dyadic_ratio(w, W), ((h, w), (H, W))
+    d = torch.as_tensor(np.asarray(data))
+    assert on_grid(d, RESIZE_GRID[0]) and float(d.abs().max()) <= RESIZE_GRID[1]
+    My, Mx = lerp_matrix(H, h), lerp_matrix(W, w)
+    sy = min(1.0, (h - 1) / (H - 1) if H > 1 and h > 1 else 1.0)
+    sx = min(1.0, (w - 1) / (W - 1) if W > 1 and w > 1 else 1.0)
+    assert np.all(My / sy == np.round(My / sy)) and np.all(Mx / sx == np.round(Mx / sx))
+    quantum = RESIZE_GRID[0] * sy * sx
+    if tuple(d.shape[2:]) == (H, W):
+        a = np.einsum('ia,ncij,jb->ncab', My, np.abs(d.double().numpy()), Mx)
+    else:
+        a = resize_forward_ref(np.abs(d.double().numpy()), H, W, False)[1]
+    top = float(a.max()) / quantum
+    assert top < LIMIT, 'resize %s -> %s: %.3g quanta' % ((h, w), (H, W), top)
+    return top
+
+
+@functools.lru_cache(maxsize=None)
+def resize_case(lo, hi, BC, dyadic):
+    """-> (x [B,2,h,w], gy [B,2,H,W]) np.float32: grid data (dyadic, guarded) or normal deviates."""
+    (h, w), (H, W) = lo, hi
+    B = BC // 2
+    gen = torch.Generator().manual_seed(seed_of('resize', lo, hi, BC, dyadic))
+    if dyadic:
+        x, gy = grid((B, 2, h, w), RESIZE_GRID[0], RESIZE_GRID[1], gen), grid((B, 2, H, W), RESIZE_GRID[0], RESIZE_GRID[1], gen)
+        resize_guard(x, h, w, H, W)
+        resize_guard(gy, h, w, H, W)
+    else:
+        x, gy = torch.randn((B, 2, h, w), generator=gen), torch.randn((B, 2, H, W), generator=gen)
+    return x.numpy(), gy.numpy()
+
+
+def _bwd_range(a, n_in, n_out):
+    """upsample_bwd_range in np.float32 -> (lo, hi)."""
+    if n_in <= 1 or n_out <= 1:
+        return 0, n_out - 1
+    inv = np.float32(n_out - 1) / np.float32(n_in - 1)
+    lo = max(0, int(np.floor(np.float32(a - 1) * inv)) - 1)
+    hi = min(n_out - 1, int(np.ceil(np.float32(a + 1) * inv)) + 1)
+    return lo, hi
+
+
+def upsample_bwd_route(h, w, H, W, BC=2):
+    """launch_upsample_backward of csrc/sgu_blend.hip read in Python -> 'group1' / 'group4' / 'group16' (+ '_notable': a footprint
+    wider than MAXNJ = 24 columns), 'wg' (+ '_notable': taller or wider than WGT = 160), 'band' (+ '_2bands': more than one column
+    band per row; '_norowtable': more than BAND_ROWS = 1024 footprint rows)."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    fp = (2 * cdiv(H, h) + 2) * (2 * cdiv(W, w) + 2)
+    ni = max(_bwd_range(a, h, H)[1] - _bwd_range(a, h, H)[0] + 1 for a in range(h))
+    nj = max(_bwd_range(b, w, W)[1] - _bwd_range(b, w, W)[0] + 1 for b in range(w))
+    if fp > 200 and w > 1 and W > 1:
+        inv = (W - 1) / (w - 1)
+        NB = min(int((512 - 8) / inv) - 1, 64, w)
+        if NB >= 1 and BC * h * cdiv(w, NB) < 2 ** 31:
+            return 'band' + ('_norowtable' if ni > 1024 else '') + ('_2bands' if cdiv(w, NB) > 1 else '')
+    if fp > 512 and BC * h * w < 2 ** 31:
+        return 'wg' + ('_notable' if ni > 160 or nj > 160 else '')
+    name = 'group16' if fp > 200 else ('group4' if fp > 16 else 'group1')
+    return name + ('_notable' if nj > 24 else '')

@@ -1,12 +1,19 @@
 """The conditions tests/test_hip_conv_exact.py rests on, checked on tests/_exact_model.py alone (no GPU, nothing from the code under
 test): the guard holds for every case list, torch's fp32 kernels in their own summation order reproduce the fp64 reference bit for
 bit (the order independence the GPU file relies on), the operands make enough outputs round / tie / hit zero for bit equality to
-mean something, and the fp16 range cases are what they claim to be."""
+mean something, and the fp16 range cases are what they claim to be.  The last section does the same for the sampling model
+(tests/test_hip_warp_exact.py, tests/test_hip_resize_exact.py): the fp32 position chain against the golden mask bits, the guards of
+the dyadic regime, the caps of the general one, route coverage, and what each backward case claims to contain."""
+import glob
+import os
+
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import _exact_model as em
+from conftest import GOLDEN, load_golden, unpack_mask
 
 DT = [pytest.param(d, id=em.DTYPE_NAMES[d]) for d in em.DTYPES]
 
@@ -323,3 +330,202 @@ def test_arena_block_is_contiguous_misaligned_and_watched():
     assert b.untouched(snap, z) and not b.untouched(snap)
     b.buf[z.storage_offset() + z.numel()] = 1.0
     assert not b.untouched(snap, z)
+
+
+# ---- sampling: what tests/test_hip_warp_exact.py and tests/test_hip_resize_exact.py rest on -------------------------------------------
+SDT = [pytest.param(d, id=em.SAMP_NAMES[d]) for d in em.SAMP_DTYPES]
+WARP_GOLDEN = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, 'warp_*.npz')))
+
+
+def shifts_of(B):
+    return (0,) if B == 1 else (0, B // 2)
+
+
+@pytest.mark.parametrize('name', WARP_GOLDEN)
+def test_taps32_reproduces_the_golden_mask_bits_and_values(name):
+    g = load_golden(name)
+    x = g['x'].numpy()
+    B, C, H, W = x.shape
+    t = em.taps32(g['flow'].numpy(), H, W)
+    assert np.array_equal(t['valid']['literal'], unpack_mask(g['mask'], (B, 1, H, W)).numpy()[:, 0])
+    for mode, key in (('literal', 'y'), ('none', 'y_nomask')):
+        ref, ra = em.warp_forward_ref(x, t, mode)
+        assert bool(em.accept_y(g[key], ref, em.gamma(4) * ra, em.F32).all()), key
+
+
+def test_rne_rounds_once():
+    v = np.array([1.0 + 2.0 ** -8 + 2.0 ** -30, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -(1.0 + 2.0 ** -8 - 2.0 ** -30), 0.0, 3.0])
+    assert em.rne(v, torch.bfloat16).double().tolist() == [1.0 + 2.0 ** -7, 1.0, 1.0 + 2.0 ** -6, -1.0, 0.0, 3.0]
+    # through fp32 the first value would lose its sticky bits, land on the tie and go down
+    assert float(torch.tensor(v[0]).float().to(torch.bfloat16)) == 1.0
+    h = np.array([1.0 + 2.0 ** -11 + 2.0 ** -30, 1.0 + 2.0 ** -11])
+    assert em.rne(h, torch.float16).double().tolist() == [1.0 + 2.0 ** -10, 1.0]
+
+
+@pytest.mark.parametrize('mode', ['literal', 'robust', None])
+def test_sampling_reference_agrees_with_the_fp64_autograd_of_the_oracle(mode):
+    from oracle import ops as oops
+    for shape, pattern in (((2, 3, 6, 20), 'rand4'), ((1, 5, 7, 13), 'const')):     # (smooth positions: the flow gradient jumps at integers)
+        c = em.warp_case(shape, em.F32, pattern, False)
+        B, C, H, W = shape
+        t = em.taps32(c['flow'], H, W)
+        m = mode or 'none'
+        x64, f64, g64 = (torch.from_numpy(c[k]).double() for k in ('x', 'flow', 'gy'))
+        y = oops.warp(x64, f64, mode)
+        if mode == 'literal':                         # (the oracle's fp64 mask is not the fp32 contract: compare on the pixels where both agree)
+            agree = torch.from_numpy(t['valid'][m])[:, None] == (oops.warp_mask(f64, H, W, mode))
+        else:
+            agree = torch.ones(B, 1, H, W, dtype=torch.bool)
+        assert float(agree.float().mean()) > 0.9
+        gxo, gfo = oops.warp_backward(x64, f64, g64 * agree, mode)
+        ref, ra = em.warp_forward_ref(c['x'], t, m)
+        # the model's weights are fp32 roundings of the fp64 ones: relative 2^-22 at most (three fp32 steps behind the position)
+        tol = lambda a: 8 * em.U32 * a + 1e-12
+        ag = agree.numpy()
+        assert np.all((np.abs(y.numpy() - ref) <= tol(ra + 4 * np.abs(c['x']).max()))[np.broadcast_to(ag, ref.shape)])
+        gx, gf, gfa = em.warp_backward_ref(c['x'], c['gy'] * ag, t, m)
+        assert np.all(np.abs(gxo.numpy() - gx) <= tol(np.abs(gx) + 16 * np.abs(c['gy']).max()))
+        assert np.all(np.abs(gfo.numpy() - gf) <= tol(gfa + 16 * C * np.abs(c['gy']).max() * np.abs(c['x']).max()))
+
+
+@pytest.mark.parametrize('dtype', SDT)
+def test_dyadic_sampling_cases_keep_their_guards_and_equal_the_plain_formula(dtype):
+    """Every dyadic case: the guard (inside warp_case); the reference through taps32 equals the plain fp64 formula (taps64) exactly;
+    the fixed-point model of gx equals the fp64 formula rounded once."""
+    for shape in em.WARP_DYADIC + em.WARP_C8_DYADIC:
+        B, C, H, W = shape
+        for pattern in sorted(set(em.FWD_PATTERNS + em.BWD_PATTERNS)):
+            c = em.warp_case(shape, dtype, pattern, True)
+            t64 = em.taps64(c['flow'], H, W)
+            for mode in em.MODES:
+                for shift in shifts_of(B):
+                    y, _ = em.warp_forward_ref(c['x'], c['t'], mode, shift)
+                    y64, _ = em.warp_forward_ref(c['x'], t64, mode, shift)
+                    assert np.array_equal(y, y64) and np.all(np.isfinite(y))
+                    assert np.array_equal(y.astype(np.float32).astype(np.float64), y)                 # exact in fp32
+                    if pattern not in em.BWD_PATTERNS:
+                        continue
+                    gx, gf, gfa = em.warp_backward_ref(c['x'], c['gy'], c['t'], mode, shift)
+                    gx64, gf64, _ = em.warp_backward_ref(c['x'], c['gy'], t64, mode, shift)
+                    assert np.array_equal(gx, gx64) and np.array_equal(gf, gf64)
+                    assert np.array_equal(gf.astype(np.float32).astype(np.float64), gf) and float(gfa.max()) * 8 * 64 < em.LIMIT
+                    got, q = em.warp_gx_model(c['gy'], c['t'], mode, shift, dtype)
+                    assert torch.equal(got, em.rne(gx, dtype)), (shape, pattern, mode, shift)
+                    assert np.array_equal(q.astype(np.float64) / em.FIX, gx)
+                    if pattern == 'nonfinite':
+                        for n, _, i, j in em.nonfinite_places(B, H, W):
+                            assert np.all(gf[n, :, i, j] == 0) and np.all(y[n, :, i, j] == 0)
+
+
+@pytest.mark.parametrize('dtype', SDT)
+def test_general_sampling_cases_rarely_have_two_candidates(dtype):
+    shapes = em.WARP_GENERAL + em.WARP_C8_GENERAL + ([em.WARP_PXT4] if dtype == em.F32 else [])
+    for shape in shapes:
+        for pattern in em.FWD_PATTERNS:
+            c = em.warp_case(shape, dtype, pattern, False)
+            for mode in em.MODES:
+                ref, ra = em.warp_forward_ref(c['x'], c['t'], mode)
+                assert np.all(np.isfinite(ref))
+                if dtype != em.F32:                   # (an fp32 output is held to the interval itself)
+                    share = em.two_candidate_share(ref, em.gamma(4) * ra, dtype)
+                    assert share <= 0.01, (shape, pattern, mode, share)
+                if pattern == 'nonfinite':
+                    for n, _, i, j in em.nonfinite_places(*c['flow'].shape[:1], *shape[2:]):
+                        assert np.all(ref[n, :, i, j] == 0)
+
+
+def test_backward_cases_hold_what_they_claim():
+    """Counted on the model: the constant flow merges lane pairs (also across lanes 63 / 64 of a wave — never — and across row ends
+    — never: counted inside), the converging flow collides, random flows put taps outside and make the masks reject pixels."""
+    for shape in em.WARP_DYADIC + em.WARP_BWD_GENERAL:
+        B, C, H, W = shape
+        dy = shape in em.WARP_DYADIC
+        for pattern in em.BWD_PATTERNS:
+            t = em.warp_case(shape, em.F32, pattern, dy)['t']
+            for mode in em.MODES:
+                n = em.warp_counts(t, mode, 0, B, H, W)
+                big = H >= 5 and W >= 9
+                if pattern == 'const' and W >= 9 and n['invalid'] < B * H * W // 2:      # (H == 1: 'robust' rejects every fy != 0)
+                    assert n['merged'] > 0, (shape, mode, n)
+                if pattern == 'converge' and H * W > 4:
+                    assert n['collisions'] > 0, (shape, mode, n)
+                if pattern == 'rand4' and big:
+                    assert n['outside'] > 0 or mode != 'none', (shape, mode, n)
+                    assert (n['invalid'] > 0) == (mode != 'none'), (shape, mode, n)
+                if pattern == 'nonfinite':
+                    assert n['invalid'] >= (0 if mode == 'none' else min(3, H * W)), (shape, mode, n)
+    # the 65-wide cases cross lane 63 / 64 inside a row, every case crosses row ends: the merge must stay off there
+    t = em.warp_case((1, 32, 9, 65), em.F32, 'const', True)['t']
+    assert 0 < em.warp_counts(t, 'none', 0, 1, 9, 65)['merged'] < 2 * 9 * 65 - 2 * (9 * 65 // 64)
+
+
+def test_every_warp_route_has_a_case():
+    fwd = set()
+    for dtype in em.SAMP_DTYPES:
+        shapes = em.WARP_DYADIC + em.WARP_GENERAL + ([em.WARP_PXT4] if dtype == em.F32 else [])
+        for B, C, H, W in shapes:
+            fwd.add((em.SAMP_NAMES[dtype], em.warp_pxt(dtype, B, C, H, W)))
+            fwd.add((em.SAMP_NAMES[dtype] + ' odd offset', em.warp_pxt(dtype, B, C, H, W, y_align=2 if dtype != em.F32 else 4)))
+    assert {('bf16', 'narrow'), ('bf16', 'pxt2'), ('bf16', 'pxt1'), ('fp16', 'pxt2'), ('fp16', 'pxt1'), ('fp32', 'pxt1'), ('fp32', 'pxt4'),
+            ('fp32', 'narrow'), ('fp32 odd offset', 'pxt1'), ('bf16 odd offset', 'pxt1')} <= fwd
+    assert em.warp_pxt(em.F32, *em.WARP_PXT4) == 'pxt4' and em.warp_pxt(em.F32, *em.WARP_PXT4, y_align=4) == 'pxt1'
+    B, C, H, W = em.WARP_PXT4
+    assert em.warp_pxt(em.F32, B, C, H // 2, W) == 'pxt1'                    # the smallest grid that takes it
+    # the pitched forms at odd W: a full pitch behind every row keeps the pair store, the admitted minimum (and one more) does not
+    assert em.warp_pxt(torch.bfloat16, 2, 5, 7, 13, 16, 16, 5 * 7 * 16) == 'pxt2' and em.warp_pxt(torch.bfloat16, 1, 5, 7, 13, 16) == 'pxt2'
+    assert em.warp_pxt(torch.bfloat16, 2, 5, 7, 13, 16, 16, 5 * 7 * 16 - 3) == 'pxt1' and em.warp_pxt(torch.bfloat16, 2, 5, 7, 13, 16, 16, 5 * 7 * 16 - 2) == 'pxt1'
+    slices = {s: em.pick_cpt(s[0], s[1], s[2] * s[3]) for s in em.WARP_DYADIC + em.WARP_BWD_GENERAL}
+    assert slices[(1, 32, 9, 65)] == (8, 4) and slices[(1, 33, 9, 65)] == (9, 4) and 33 % 9 != 0          # a short last slice
+    assert slices[(2, 16, 13, 26)][1] == 2 and slices[(1, 3, 5, 9)][1] == 1
+
+
+def test_every_resize_route_has_a_case():
+    want = {'group1', 'group4', 'group16', 'group16_notable', 'wg', 'wg_notable', 'band', 'band_2bands', 'band_norowtable'}
+    got = set()
+    for name, (lo, hi) in em.RESIZE_BWD_ROUTES:
+        for bc in em.RESIZE_BC:
+            assert em.upsample_bwd_route(*lo, *hi, bc) == name, (name, lo, hi)
+        got.add(name)
+    assert got == want
+    assert any(hi[1] == 1 for _, (lo, hi) in em.RESIZE_BWD_ROUTES) and any(lo[1] == 1 for _, (lo, hi) in em.RESIZE_BWD_ROUTES)
+    # what the older tolerance test reaches (its comment once claimed the fallback loops)
+    old = [((6, 20), (12, 40)), ((4, 13), (256, 832)), ((64, 208), (256, 832)), ((1, 3), (7, 9)), ((5, 1), (11, 6)), ((24, 40), (9, 15)), ((3, 5), (3, 5)),
+           ((32, 104), (256, 832)), ((16, 52), (256, 832)), ((6, 5), (6, 200)), ((2, 3), (400, 12))]
+    assert {em.upsample_bwd_route(*lo, *hi, 6) for lo, hi in old} <= {'group1', 'group4', 'band', 'band_2bands'}
+
+
+def test_the_backward_range_brackets_every_weight_with_room_to_spare():
+    """upsample_bwd_range is generous on purpose: no non-zero weight lies beyond ceil((a + 1) * inv) or below floor((a - 1) * inv) - 1,
+    so its outermost `+ 1` is slack and a range without it computes the same sums (why no test can tell that variant apart)."""
+    for n_in in list(range(2, 34)) + [52, 104]:
+        for n_out in list(range(2, 131)) + [513, 832, 1025]:
+            i0, i1, l0, l1 = em.lerp32(n_out, n_in)
+            inv = np.float32(n_out - 1) / np.float32(n_in - 1)
+            a = np.arange(n_in)
+            hi = np.minimum(n_out - 1, np.ceil((a + 1).astype(np.float32) * inv).astype(np.int64))
+            lo = np.maximum(0, np.floor((a - 1).astype(np.float32) * inv).astype(np.int64) - 1)
+            j = np.arange(n_out)
+            for idx, l in ((i0, l0), (i1, l1)):
+                assert not np.any(((j > hi[idx]) | (j < lo[idx])) & (l != 0)), (n_in, n_out)
+            for b in (0, n_in - 1):
+                assert em._bwd_range(b, n_in, n_out)[0] <= lo[b] and em._bwd_range(b, n_in, n_out)[1] >= hi[b]
+
+
+def test_dyadic_resize_cases_keep_their_guard_and_general_ones_are_general():
+    for lo, hi in em.RESIZE_FWD_DYADIC + [c for _, c in em.RESIZE_BWD_ROUTES]:
+        for bc in em.RESIZE_BC:
+            x, gy = em.resize_case(lo, hi, bc, True)                          # (guards inside)
+            for rate in (False, True):
+                y, _ = em.resize_forward_ref(x, hi[0], hi[1], rate)
+                gx, _, nnz = em.resize_backward_ref(gy, lo[0], lo[1], rate)
+                assert np.all(np.isfinite(y)) and np.all(np.isfinite(gx)) and int(nnz.max()) >= 1
+                if not rate:
+                    assert np.array_equal(y.astype(np.float32).astype(np.float64), y) and np.array_equal(gx.astype(np.float32).astype(np.float64), gx)
+    for lo, hi in em.RESIZE_FWD_GENERAL + em.RESIZE_BWD_GENERAL:
+        assert not (em.is_dyadic_ratio(lo[0], hi[0]) and em.is_dyadic_ratio(lo[1], hi[1]))
+    # the adjoint really is the adjoint of the forward: <resize(x), gy> == <x, adjoint(gy)> in fp64
+    x, gy = em.resize_case((4, 13), (64, 208), 6, False)
+    y, _ = em.resize_forward_ref(x, 64, 208, True)
+    gx, _, _ = em.resize_backward_ref(gy, 4, 13, True)
+    a, b = float((y * gy).sum()), float((gx * x).sum())
+    assert abs(a - b) <= 1e-10 * max(1.0, abs(a))

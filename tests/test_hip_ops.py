@@ -498,8 +498,9 @@ def test_flow_update_matches_torch_chain(dtype):
 
 @pytest.mark.parametrize('shape', [((6, 20), (12, 40)), ((4, 13), (256, 832)), ((64, 208), (256, 832)), ((1, 3), (7, 9)),
                                    ((5, 1), (11, 6)), ((24, 40), (9, 15)), ((3, 5), (3, 5)),
-                                   # 8x (16 lanes per input pixel), 16x (workgroup variant with weight tables), footprints wider than the
-                                   # group kernel's column table / taller than the workgroup kernel's tables (their fallback loops)
+                                   # 8x, 16x and extreme ratios: since the band kernel took every footprint > 200 with w > 1 and W > 1
+                                   # over, these run in it (one and several column bands); the shapes here reach only group<1>, group<4>
+                                   # and the band kernel.  group<16>, the workgroup kernel and every no-table loop: tests/test_hip_resize_exact.py
                                    ((32, 104), (256, 832)), ((16, 52), (256, 832)), ((6, 5), (6, 200)), ((2, 3), (400, 12))])
 @pytest.mark.parametrize('if_rate', [True, False])
 def test_flow_upsample_backward_matches_autograd(shape, if_rate):

@@ -326,7 +326,10 @@ extern "C" int upf_warp_forward_pitched(const void* x, long long x_batch_stride,
   //  [4,32,96,320]: every gather instruction then spans 4x the cache lines; fp32 gained 12 %: kept for fp32 only)
   // pixel pairs / quads: the OUTPUT rows must keep them aligned and hold the rounded-up row (W % n == 0, or pitch padding behind it)
   const bool four = (dtype == UPF_F32) && (yp % 4 == 0) && (W % 4 == 0) && aligned_to(y, 16) && ybs % 4 == 0 && (long long)B * HW >= 4 * 64 * 256;
-  const bool two = !four && (dtype != UPF_F32) && (yp % 2 == 0) && aligned_to(y, 4) && ybs % 2 == 0;     // (yp even => yp >= W rounded up to 2)
+  // (yp even => yp >= W rounded up to 2.)  At an odd W the pair store of a row's last pixel also writes column W, the first padding
+  // column — of the LAST row too.  The admitted minimum batch stride leaves that row's padding out of the buffer, so the pair
+  // stores are taken only where the stride promises the full pitch behind every row (include/upflow_hip.h); else one pixel per thread.
+  const bool two = !four && (dtype != UPF_F32) && (yp % 2 == 0) && aligned_to(y, 4) && ybs % 2 == 0 && (W % 2 == 0 || ybs >= (long long)C * H * yp);
   const int pxt = four ? 4 : (two ? 2 : 1);
   const int ngroups = H * cdiv(W, pxt);
   const int cpt = warp::pick_cpt(B, C, ngroups);
