@@ -81,13 +81,11 @@ WATERFALL = re.compile(r's_and_saveexec_b64[^\n]*\n[^\n]*buffer_(?:load|store)_[
 def test_no_waterfall_loops_in_the_hot_kernels(disassembly):
     """hipcc wraps a buffer access whose DESCRIPTOR it considers divergent in a waterfall loop (v_readfirstlane x4,
     v_cmp x2, exec juggling, a branch) — the weight-gradient kernel's staging waves carried 13 of them per tile for three rounds
-    because its tile decode divides on the vector unit.  The default kernels must have none (the descriptors are made uniform
-    explicitly); the regression shows in the disassembly long before it shows in a benchmark."""
+    because its tile decode divides on the vector unit.  No kernel of these sources may have one (the descriptors are made
+    uniform explicitly); the regression shows in the disassembly long before it shows in a benchmark."""
     bad = {}
     for src in ('conv_wgrad.hip', 'conv3x3.hip', 'conv_c8.hip', 'corr81_fwd.hip', 'corr81_bwd.hip', 'warp.hip', 'sgu_blend.hip', 'misc.hip', 'loss.hip'):
         for name, body in _functions(disassembly[src]).items():
-            if src == 'conv_wgrad.hip' and 'wgrad_pc_kernel' not in name and 'reduce' not in name and 'act_grad' not in name:
-                continue                              # (wgrad_kernel, the UPF_WGRAD_MODE=1 A/B kernel, is not on the default path)
             n = len(WATERFALL.findall(body))
             if n:
                 bad[name[:80]] = n

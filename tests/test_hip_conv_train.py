@@ -153,6 +153,31 @@ def test_wgrad_multi_level(cfg, dtype):
     assert (one - ref1).abs().max() <= 2e-4 * max(1.0, float(ref1.abs().max()))
 
 
+def test_wgrad_one_launch_per_co_block():
+    """The route of the wide decoder layers, which the cases above are too small to reach: conv_wgrad.hip launches the co blocks
+    of a layer SEPARATELY when pc_split_co holds (nco2 > 1, nco2 * nci2 > 16 block pairs, nci2 <= 16) and the levels have at least
+    256 tiles of 4 rows x 32 pixels.  520 -> 70 channels: nci2 = ceil(520 / 64) = 9, nco2 = ceil(70 / 64) = 2, 18 pairs; the level
+    (2, 64, 256) has 2 x ceil(256 / 32) x ceil(64 / 4) = 256 tiles, and (2, 8, 26) — ragged — adds 4, so the shifted staging runs
+    in the split launches too (the single-use call below is the aligned kernel on the same route).  The plan itself is pinned
+    by test_wgrad_plan_cpu.py.  Same reference and bound as test_wgrad_multi_level; deterministic."""
+    from upflow_pytorch_amd import ops
+    Cin, Cout, k, d, dtype = 520, 70, 3, 1, torch.bfloat16
+    g = torch.Generator().manual_seed(Cin + Cout + d)
+    uses, ref = [], 0
+    for (B, H, W) in [(2, 64, 256), (2, 8, 26)]:
+        xw = torch.randn(B, Cin + 3, H, W, generator=g).to(dtype).cuda()
+        gw_ = (torch.randn(B, Cout + 2, H, W, generator=g) * 0.25).to(dtype).cuda()
+        x, gy = xw[:, 3:], gw_[:, :Cout]
+        uses.append((x, gy))
+        ref = ref + torch.nn.grad.conv2d_weight(x.float(), (Cout, Cin, k, k), gy.float(), padding=d * (k - 1) // 2, dilation=d)
+    got = ops.conv_wgrad_multi(uses, Cin, Cout, k, d)
+    assert got.shape == ref.shape and (got - ref).abs().max() <= 2e-4 * max(1.0, float(ref.abs().max())), float((got - ref).abs().max())
+    assert torch.equal(got, ops.conv_wgrad_multi(uses, Cin, Cout, k, d))
+    one = ops.conv_wgrad_multi(uses[:1], Cin, Cout, k, d)
+    ref1 = torch.nn.grad.conv2d_weight(uses[0][0].float(), (Cout, Cin, k, k), uses[0][1].float(), padding=d * (k - 1) // 2, dilation=d)
+    assert (one - ref1).abs().max() <= 2e-4 * max(1.0, float(ref1.abs().max()))
+
+
 @pytest.mark.parametrize('cfg', [(3, 16, 3, 1, 4), (12, 16, 3, 1, 8), (16, 16, 3, 2, 4), (16, 32, 3, 1, 8), (32, 32, 1, 1, 2), (16, 3, 3, 1, 4), (16, 16, 3, 1, 6)])
 def test_wgrad_of_narrow_layers(cfg):
     """Layers with <= 32 input and output channels (the feature pyramid's first levels, the heads): aligned and ragged widths,

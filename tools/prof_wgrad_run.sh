@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC picture of wgrad_kernel for one layer shape: bash tools/prof_wgrad_run.sh "567 128 1"  (writes gpurun_out/prof_wgrad/*)
+# PMC picture of wgrad_pc_kernel for one layer shape: bash tools/prof_wgrad_run.sh "567 128 1"  (writes prof_wgrad/* in the output directory set below)
 # (SQ counters only: a pass with TCC_*_sum counters did not terminate on this pool.)
 R=$(pwd); export TMPDIR=/tmp
 cfg=${1:-"567 128 1"}; tag=$(echo $cfg | tr ' ' '_')

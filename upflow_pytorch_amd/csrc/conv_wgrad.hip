@@ -12,9 +12,9 @@
 // NCHW stores them: tiles are staged into LDS with plain 16-byte copies (no register transposition, unlike the forward
 // kernel whose K is the channel dimension).
 //
-//   * workgroup = 4 waves = a 64 co x 64 ci block of dW (wave w: co block w&1, ci block w>>1), all taps: 9 x 16
-//     accumulator registers per lane; grid = (K-split, block pairs).  A workgroup walks its share of the pixel tiles and
-//     writes ONE partial block at the end; partials are summed in fixed order by a second kernel (deterministic).
+//   * workgroup = a 64 co x 64 ci block of dW, all taps: four waves multiply (9 x 16 accumulator registers per lane), four
+//     more stage the tiles for them (wgrad_pc_kernel); grid = K-splits x block pairs.  A workgroup walks its share of the pixel
+//     tiles and writes ONE partial block at the end; partials are summed in fixed order by a second kernel (deterministic).
 //   * pixel tile = TR rows x 32 pixels.  Dilation by ROW PHASE: the TR rows of a tile are d image rows apart, so the
 //     three kernel rows read TR + 2 staged rows of X whatever d is; horizontally the taps are windows shifted by -d, 0,
 //     +d pixels inside the staged rows: whole 8-pixel blocks for d = 8, 16, dword selects for d = 2, 4, and a 2-byte
@@ -85,13 +85,6 @@ __device__ __forceinline__ uint4 window(const uint4& p2, const uint4& p1, const 
                       __builtin_amdgcn_alignbyte(c.w, c.z, 2), __builtin_amdgcn_alignbyte(n1.x, c.w, 2));
 }
 
-// partial: [ksplit][tap][pad64(Cout)][pad64(Cin)] fp32
-// One workgroup per CU (512 registers per wave): 144 accumulators + the NEXT tile's staging data in registers — the global
-// loads of tile t+1 are issued before the 72 MFMAs of tile t and written to LDS after them, so the matrix pipe only waits
-// for two barriers and 13 ds_write_b128 per tile (the first version loaded, waited, computed: ~25 % MFMA utilisation).
-// RAGGED (any W >= 8, any alignment): the 8-pixel block that straddles the row end is loaded shifted left so that it
-// ENDS at the row end (2-byte-aligned 16-byte buffer loads are legal on gfx950) and shifted back in registers, zeros
-// filling the pixels beyond the row.
 // a wave-uniform pointer, in scalar registers whatever the compiler's divergence analysis concluded
 template <typename P> __device__ __forceinline__ P* uniform_ptr(P* p) {
   const unsigned long long v = (unsigned long long)p;
@@ -112,232 +105,41 @@ __device__ __forceinline__ u32x4 shr_pixels(u32x4 v, int sh) {            // 128
 // The K dimension of one launch may span several PYRAMID LEVELS: the decoder's weights are shared by all levels
 // (model/upflow.py:535-573 calls the same flow_estimators / context_networks five times), so their weight gradient is one
 // contraction over the pixels of every level.  A launch takes up to MAXL (x, g) pairs of different sizes; tile indices run
-// through the levels back to back (tile0 = first tile of a level) and a workgroup's tiles ks_id, ks_id + ksplit, ... are
-// spread over all of them.
+// through the levels back to back (tile0 = first tile of a level) and a workgroup's slice of the tile range may cross from
+// one level into the next.
 constexpr int MAXL = 6, LT_STRIDE = 16;                  // (LT_STRIDE: ints per row of wgrad_pc_kernel's level table in LDS)
 struct KLevel {
   const void* x; const void* g;
   long long xbs, gbs;
-  int H, W, tiles_x, tiles_y, tile0, ragged;     // ragged: rows / bases not 16-byte aligned (wgrad_pc_kernel<.., RAGGED = true> only)
+  int H, W, tiles_x, tiles_y, tile0, ragged;     // ragged: rows / bases not 16-byte aligned (read by wgrad_pc_kernel<.., RAGGED = true>)
 };
 struct KLevels {
   KLevel lv[MAXL];
   int n, ntiles;
 };
 
-// MB = 1: 4 waves, 64 co x 64 ci per workgroup;  MB = 2: 8 waves (two per SIMD, 256 registers each), 128 co x 64 ci.  The
-// kernel is bound by its staging traffic (~53 KB per tile and workgroup at MB = 1, the X tile re-fetched by every co
-// block): with 128 co per workgroup the X tile — the larger operand, with its halo — is fetched ONCE for Cout <= 128.
-// (288 accumulators per lane in 4 waves were tried first: the allocator spills 100-200 registers per lane.)
-template <typename T, int D, bool RAGGED, int MB>
-__global__ __launch_bounds__(NTHREADS * MB, MB)
-void wgrad_kernel(const KLevels L, float* __restrict__ partial, int Cin, int Cout, int nci2, int J) {
-  using G = Geo<D>;
-  constexpr int COB = 64 * MB;                                             // output channels per workgroup
-  constexpr int DD = (D == 0) ? 1 : D;
-  constexpr int HALO = halo_of(D);
-  constexpr int NTH = NTHREADS * MB;
-  constexpr int NXT = (64 * G::XR * G::XB + NTH - 1) / NTH;                // X staging tasks per thread (9; 12 for D = 16; half with 8 waves)
-  constexpr int NGT = (COB * TR * G::GB + NTH - 1) / NTH;                  // g staging tasks per thread (4)
-  extern __shared__ __attribute__((aligned(16))) uint4 smem[];
-  uint4* xs = smem;
-  uint4* gs = smem + G::X_BLOCKS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // XCD-aware decomposition.  Workgroup L runs on XCD L % 8 (round-robin dispatch).  Each XCD owns a contiguous EIGHTH of
-  // the tile range and runs, side by side, every (co block, ci block) pair of J consecutive tiles: the co blocks of a
-  // tile share its X slab, the ci blocks its g slab, horizontally adjacent tiles their halo sectors — all through that
-  // XCD's L2, so the fabric carries every byte about once.  (The first mapping — K-split index = blockIdx.x — spread the
-  // sharers over all XCDs: every layer ran at the ~3.7 TB/s this access pattern gets from HBM / MALL, 3.8 us per tile
-  // whatever its shape, a quarter of the MFMA rate.)  K-split slot (partial block) = xcd * J + j.
-  const int nblocks = gridDim.x / (8 * J);
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int bpair = slot % nblocks, jj = slot / nblocks;
-  const int ks_id = xcd * J + jj;
-  const int co2 = bpair / nci2, ci2 = bpair - co2 * nci2;                // (COB-channel co block, 64-channel ci block) of this workgroup
-  const int cob = wave % (2 * MB), cib = wave / (2 * MB);
-  const int ch = lane & 31, kg = lane >> 5;
-  const int t_lo = (int)((long long)L.ntiles * xcd / 8), t_hi = (int)((long long)L.ntiles * (xcd + 1) / 8);   // this XCD's tiles
-  const int cop = (Cout + COB - 1) / COB * COB, cip = (Cin + 63) / 64 * 64;
-  const uint32_t xnch = (uint32_t)max(min(Cin - ci2 * 64, 64), 0), gnch = (uint32_t)max(min(Cout - co2 * COB, COB), 0);
-
-  // per-thread staging geometry (the same for every tile), one packed word per task:
-  // LDS slot (12 bits, 0xfff = no task) | channel << 12 (7 bits) | staged row << 19 (4 bits) | 8-pixel block << 23
-  int xg[NXT], gg[NGT];
-#pragma unroll
-  for (int i = 0; i < NXT; ++i) {
-    const int t = tid + i * NTH;
-    const int c = t / (G::XR * G::XB), rem = t - c * (G::XR * G::XB), sr = rem / G::XB, bb = rem - sr * G::XB;
-    xg[i] = ((t < 64 * G::XR * G::XB) ? c * G::XCH + sr * G::XB + bb : 0xfff) | (c << 12) | (sr << 19) | (bb << 23);
-  }
-#pragma unroll
-  for (int i = 0; i < NGT; ++i) {
-    const int t = tid + i * NTH;
-    const int c = t / (TR * G::GB), rem = t - c * (TR * G::GB), k = rem / G::GB, bb = rem - k * G::GB;
-    gg[i] = ((t < COB * TR * G::GB) ? c * G::GCH + k * G::GB + bb : 0xfff) | (c << 12) | (k << 19) | (bb << 23);
-  }
-  static_assert(64 * G::XCH < 0xfff && 128 * G::GCH < 0xfff, "LDS slot index must fit 12 bits");
-  u32x4 px[NXT], pg[NGT];
-  int sx[RAGGED ? NXT : 1], sg[RAGGED ? NGT : 1];                         // RAGGED: left shift of each staged block
-  auto issue = [&](int tile) {                                           // global loads of one tile -> registers
-    // the level this (uniform) tile index belongs to: scalar selects over the kernel arguments
-    const T* x = (const T*)L.lv[0].x; const T* g = (const T*)L.lv[0].g;
-    long long xbs = L.lv[0].xbs, gbs = L.lv[0].gbs;
-    int H = L.lv[0].H, W = L.lv[0].W, tiles_x = L.lv[0].tiles_x, tiles_y = L.lv[0].tiles_y, t0 = 0;
-#pragma unroll
-    for (int i = 1; i < MAXL; ++i)
-      if (i < L.n && tile >= L.lv[i].tile0) {
-        x = (const T*)L.lv[i].x; g = (const T*)L.lv[i].g; xbs = L.lv[i].xbs; gbs = L.lv[i].gbs;
-        H = L.lv[i].H; W = L.lv[i].W; tiles_x = L.lv[i].tiles_x; tiles_y = L.lv[i].tiles_y; t0 = L.lv[i].tile0;
-      }
-    const int lt = tile - t0;
-    const int tx = lt % tiles_x, ty = (lt / tiles_x) % tiles_y, n = lt / (tiles_x * tiles_y);
-    const int phase = ty % DD, q = ty / DD;
-    const int y0 = phase + DD * q * TR, x0 = tx * TWP;                  // output rows y0 + k*DD, k < TR
-    const bool live = tile < t_hi;
-    const uint32_t plane = (uint32_t)H * (uint32_t)W * 2u;
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x + (size_t)n * xbs + (size_t)ci2 * 64 * H * W), 0, live ? xnch * plane : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(g + (size_t)n * gbs + (size_t)co2 * COB * H * W), 0, live ? gnch * plane : 0u, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < NXT; ++i) {
-      const int xc = (xg[i] >> 12) & 127, xsr = (xg[i] >> 19) & 15, xb8 = xg[i] >> 23;
-      const int gy = (D == 0) ? y0 + xsr : y0 + (xsr - 1) * DD, gx = x0 - HALO + 8 * xb8;
-      const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-      int sh = 0;
-      if constexpr (RAGGED) { sh = (in && gx + 8 > W) ? gx + 8 - W : 0; sx[i] = sh; }
-      const uint32_t off = in ? (uint32_t)xc * plane + (uint32_t)(gy * W + gx - sh) * 2u : 0x80000000u;
-      px[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < NGT; ++i) {
-      const int gc = (gg[i] >> 12) & 127, gk = (gg[i] >> 19) & 15, gb8 = gg[i] >> 23;
-      const int gy = y0 + gk * DD, gx = x0 + 8 * gb8;
-      const bool in = gy < H && gx < W;
-      int sh = 0;
-      if constexpr (RAGGED) { sh = (in && gx + 8 > W) ? gx + 8 - W : 0; sg[i] = sh; }
-      const uint32_t off = in ? (uint32_t)gc * plane + (uint32_t)(gy * W + gx - sh) * 2u : 0x80000000u;
-      pg[i] = __builtin_amdgcn_raw_buffer_load_b128(gr, off, 0, 0);
-    }
-  };
-  auto land = [&]() {                                                    // registers -> LDS
-#pragma unroll
-    for (int i = 0; i < NXT; ++i)
-      if ((xg[i] & 0xfff) != 0xfff) xs[xg[i] & 0xfff] = __builtin_bit_cast(uint4, RAGGED ? shr_pixels(px[i], sx[RAGGED ? i : 0]) : px[i]);
-#pragma unroll
-    for (int i = 0; i < NGT; ++i)
-      if ((gg[i] & 0xfff) != 0xfff) gs[gg[i] & 0xfff] = __builtin_bit_cast(uint4, RAGGED ? shr_pixels(pg[i], sg[RAGGED ? i : 0]) : pg[i]);
-  };
-
-  f32x16 acc[G::NT];
-#pragma unroll
-  for (int t = 0; t < G::NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-
-  issue(t_lo + jj);
-  land();
-  __syncthreads();
-  const uint4* xw = xs + (cib * 32 + ch) * G::XCH;
-  const uint4* gw = gs + (cob * 32 + ch) * G::GCH;
-  for (int tile = t_lo + jj; tile < t_hi; tile += J) {
-    issue(tile + J);                                                     // (beyond the last tile: a null descriptor, zeros)
-    // ---- matrix work on the tile in LDS.  The LDS reads of staged row s+1 (and of the next k-step's g operands) are issued
-    // BEFORE the MFMAs of row s: left to itself hipcc places each ds_read right before its first use, and with one wave
-    // per SIMD nothing else hides the ~130-cycle LDS latency — the matrix pipe idled three quarters of the time.
-    if constexpr (D == 0) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int blk = 2 * ks + kg;                                     // this lane's 8-pixel block inside the 32-pixel row
-#pragma unroll
-        for (int k = 0; k < TR; ++k) acc[0] = Mma32<T>::mma(gw[k * G::GB + blk], xw[k * G::XB + blk], acc[0]);
-      }
-    } else if constexpr (MB == 2) {
-      // two waves per SIMD on 256 registers each: they cover for each other's LDS latency (reading ahead would spill)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int blk = 2 * ks + kg;
-        uint4 a[TR];
-#pragma unroll
-        for (int k = 0; k < TR; ++k) a[k] = gw[k * G::GB + blk];
-#pragma unroll
-        for (int s2 = 0; s2 < G::XR; ++s2) {
-          const uint4* row = xw + s2 * G::XB + HALO / 8 + blk;
-          uint4 p2 = make_uint4(0, 0, 0, 0), n2 = p2;
-          const uint4 p1 = row[-1], c = row[0], n1 = row[1];
-          if constexpr (D == 16) { p2 = row[-2]; n2 = row[2]; }
-          const uint4 w0 = window<DD>(p2, p1, c, n1, n2), w2 = window<-DD>(p2, p1, c, n1, n2);
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
-            const int k = s2 - ky;
-            if (k >= 0 && k < TR) {
-              acc[ky * 3 + 0] = Mma32<T>::mma(a[k], w0, acc[ky * 3 + 0]);
-              acc[ky * 3 + 1] = Mma32<T>::mma(a[k], c, acc[ky * 3 + 1]);
-              acc[ky * 3 + 2] = Mma32<T>::mma(a[k], w2, acc[ky * 3 + 2]);
-            }
-          }
-        }
-      }
-    } else {
-      struct Row { uint4 p2, p1, c, n1, n2; };
-      auto rload = [&](int ks, int s2) {
-        const uint4* row = xw + s2 * G::XB + HALO / 8 + 2 * ks + kg;
-        Row r;
-        r.p2 = r.n2 = make_uint4(0, 0, 0, 0);
-        r.p1 = row[-1]; r.c = row[0]; r.n1 = row[1];
-        if constexpr (D == 16) { r.p2 = row[-2]; r.n2 = row[2]; }
-        return r;
-      };
-      uint4 a[2][TR];
-#pragma unroll
-      for (int k = 0; k < TR; ++k) a[0][k] = gw[k * G::GB + kg];
-      Row cur = rload(0, 0);
-#pragma unroll
-      for (int it = 0; it < 2 * G::XR; ++it) {
-        const int ks = it / G::XR, s2 = it % G::XR;
-        Row nxt = cur;
-        if (it + 1 < 2 * G::XR) nxt = rload((it + 1) / G::XR, (it + 1) % G::XR);
-        if (ks == 0 && s2 == 0) {
-#pragma unroll
-          for (int k = 0; k < TR; ++k) a[1][k] = gw[k * G::GB + 2 + kg];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const uint4 w0 = window<DD>(cur.p2, cur.p1, cur.c, cur.n1, cur.n2), w2 = window<-DD>(cur.p2, cur.p1, cur.c, cur.n1, cur.n2);
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const int k = s2 - ky;                                         // staged row s2 = output row k + kernel row ky
-          if (k >= 0 && k < TR) {
-            acc[ky * 3 + 0] = Mma32<T>::mma(a[ks][k], w0, acc[ky * 3 + 0]);
-            acc[ky * 3 + 1] = Mma32<T>::mma(a[ks][k], cur.c, acc[ky * 3 + 1]);
-            acc[ky * 3 + 2] = Mma32<T>::mma(a[ks][k], w2, acc[ky * 3 + 2]);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        cur = nxt;
-      }
-    }
-    __syncthreads();                                                     // every wave is done reading this tile
-    land();
-    __syncthreads();
-  }
-  // ---- partial block: D layout col = lane & 31 (ci), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (co)
-  float* pb = partial + (size_t)ks_id * G::NT * cop * cip;
-  const int ci = ci2 * 64 + cib * 32 + ch;
-#pragma unroll
-  for (int t = 0; t < G::NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = co2 * COB + cob * 32 + (e & 3) + 8 * (e >> 2) + 4 * kg;
-      pb[((size_t)t * cop + co) * cip + ci] = acc[t][e];
-    }
-}
-
-// ---- producer / consumer form -------------------------------------------------------------------------------------------
-// PMC picture of wgrad_kernel (profiles/r02_wgrad_567_128_pmc.txt): 11 K cycles per tile and SIMD against 4.6 K of MFMA issue —
-// every wave stages (address arithmetic, loads, LDS writes), waits at a workgroup barrier, multiplies, waits again: the
-// phases of all waves coincide, so the matrix pipe idles while the tile is staged.  Here the roles are split: waves 0-3
-// (consumers) only read LDS and issue MFMAs, waves 4-7 (producers) only stage — loads of tile t+3 in flight in one of two
-// register sets while tile t+1 is written to the OTHER of two LDS buffers — so that a SIMD always holds one wave of each
-// kind and issues MFMAs and staging instructions side by side; one barrier per tile swaps the buffers.  64 co x 64 ci per
-// workgroup, same partial layout, same XCD-aware tile order as wgrad_kernel<.., MB = 1>.
+// ---- the weight-gradient kernel: producer / consumer form ------------------------------------------------------------------
+// The first form of this kernel had every wave do everything.  Its PMC picture (profiles/r02_wgrad_567_128_pmc.txt): 11 K cycles
+// per tile and SIMD against 4.6 K of MFMA issue — every wave stages (address arithmetic, loads, LDS writes), waits at a
+// workgroup barrier, multiplies, waits again: the phases of all waves coincide, so the matrix pipe idles while the tile is
+// staged.  (Fetching the X tile once per 128 co with 288 accumulators per lane in 4 waves was tried too: the allocator spills
+// 100-200 registers per lane.)
+// Here the roles are split: waves 0-3 (consumers) only read LDS and issue MFMAs, waves 4-7 (producers) only stage — loads of
+// tile t+3 in flight in one of two register sets while tile t+1 is written to the OTHER of two LDS buffers — so that a SIMD
+// always holds one wave of each kind and issues MFMAs and staging instructions side by side; one barrier per tile swaps the
+// buffers.  64 co x 64 ci per workgroup (consumer wave w: co block w & 1, ci block w >> 1), all taps: 9 x 16 accumulator
+// registers per lane.
+// XCD-aware decomposition.  Workgroup b runs on XCD b % 8 (round-robin dispatch).  With NS = 8 slices each XCD owns a contiguous
+// EIGHTH of the tile range and runs, side by side, every (co block, ci block) pair of J consecutive tiles: the co blocks of a
+// tile share its X slab, the ci blocks its g slab, horizontally adjacent tiles their halo sectors — all through that XCD's L2,
+// so the fabric carries every byte about once.  (The first mapping — K-split index = blockIdx.x — spread the sharers over all
+// XCDs: every layer ran at the ~3.7 TB/s this access pattern gets from HBM / MALL, 3.8 us per tile whatever its shape, a
+// quarter of the MFMA rate.)
+// Partial blocks: a workgroup writes ONE 64 x 64 x taps fp32 block at the end, into K-split slot = slice * J + j of
+// partial[NS * J][tap][pad64(Cout)][pad64(Cin)]; wgrad_reduce_kernel sums the slots in fixed order (deterministic).
+// Shifted loads (any W >= 8, any alignment): on a ragged level the 8-pixel block that straddles the row end is loaded shifted
+// left so that it ENDS at the row end (2-byte-aligned 16-byte buffer loads are legal on gfx950) and shifted back in registers
+// (shr_pixels), zeros filling the pixels beyond the row.
 // RAGGED here = "some level of this launch is ragged" (KLevel::ragged says which): the producers pick the shifted staging
 // PER TILE by a wave-uniform branch, so aligned and ragged pyramid levels share one launch, one accumulation and one set
 // of partial blocks.  (Round 4 gave the ragged levels — 52, 26, 13 pixels wide, 6 % of a config-3 step's pixels — their own
@@ -354,7 +156,7 @@ void wgrad_pc_kernel(const KLevels L, float* __restrict__ partial, int Cin, int 
   constexpr int BUF = G::X_BLOCKS + G::G_BLOCKS;                            // 16-byte blocks per LDS buffer
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];            // two buffers: [X | g] [X | g]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // J_ns = J | NS << 16: the tile range is cut into NS slices (8 = one per XCD, the mapping described at wgrad_kernel; fewer for
+  // J_ns = J | NS << 16: the tile range is cut into NS slices (8 = one per XCD, the decomposition described above; fewer for
   // the layers whose K is a handful of tiles: see pick_split) and J workgroups per block pair walk a slice side by side
   const int J = J_ns & 0xffff, NS = J_ns >> 16;
   const int nblocks = gridDim.x / (NS * J);
@@ -875,113 +677,35 @@ void act_grad_kernel(const T* __restrict__ src, long long sbs, const T* __restri
 
 __global__ void bias_grad_multi_final_kernel(const BiasParts P, int Cout) { bias_finish(P, blockIdx.x * blockDim.x + threadIdx.x, Cout); }
 
-// K-splits = 8 XCDs x J: J concurrent tiles per XCD such that J x (block pairs) workgroups fill its 32 CUs (the kernel
-// keeps a whole tile in registers: 1 workgroup per CU is resident), bounded by the tiles an XCD has and by 40 MB of fp32
-// partial blocks per 64 output channels of a workgroup.
-// kernel choice: 0 = producer / consumer kernel (64 co x 64 ci), 1 = wgrad_kernel (64 co, or 128 co for Cout > 64);
-// UPF_WGRAD_MODE overrides (A/B runs)
-static int wgrad_mode() {
-  static const int m = [] { const char* e = getenv("UPF_WGRAD_MODE"); return e ? atoi(e) : 0; }();
-  return m;
-}
-static int co_block(int Cout) { return (wgrad_mode() == 1 && Cout > 64) ? 128 : 64; }
-static int pick_ksplit(int ntiles, int nblocks, int ntaps, int cob) {
-  int J = 32 / nblocks;
-  const long long per_split = (long long)nblocks * ntaps * cob * 64 * 4;
-  const int cap = (int)(((40ll << 20) * (cob / 64)) / (8 * per_split));
-  if (J > cap) J = cap;
-  if (J > (ntiles + 7) / 8) J = (ntiles + 7) / 8;
-  return 8 * (J < 1 ? 1 : J);
-}
-
-// One group of levels (all aligned, or all through the RAGGED staging) -> `ksplit` partial blocks starting at `ws`.
-template <typename T, int D, bool RAGGED, int MB>
-void launch_group(const upf_wgrad_level* lv, const int* idx, int n, float* ws, int ksplit, int Cin, int Cout, hipStream_t stream) {
-  using G = Geo<D>;
-  constexpr int DD = (D == 0) ? 1 : D;
+// ---- host side: level table -> plan -> one launch (or one per co block) -> reduction ----------------------------------------------
+// The level table the kernel takes, from the caller's levels (D: the kernel's template value, 0 for 1x1): default batch strides,
+// the tile grid of every level (TR rows d image rows apart: tiles_y counts d row phases), tile0 and whether the level needs the
+// shifted staging.  The planner and the launch both read THIS table.
+static KLevels make_levels(const upf_wgrad_level* lv, int n, int Cin, int Cout, int D) {
+  const int dd = D == 0 ? 1 : D;
   KLevels L;
   memset(&L, 0, sizeof(L));
-  int t0 = 0;
   for (int i = 0; i < n; ++i) {
-    const upf_wgrad_level& a = lv[idx[i]];
+    const upf_wgrad_level& a = lv[i];
     KLevel& k = L.lv[i];
     k.x = a.x; k.g = a.grad_pre;
     k.xbs = a.x_batch_stride ? a.x_batch_stride : (long long)Cin * a.H * a.W;
     k.gbs = a.g_batch_stride ? a.g_batch_stride : (long long)Cout * a.H * a.W;
     k.H = a.H; k.W = a.W;
-    k.tiles_x = cdiv(a.W, TWP); k.tiles_y = DD * cdiv(cdiv(a.H, DD), TR);
-    k.tile0 = t0;
-    t0 += a.B * k.tiles_x * k.tiles_y;
+    k.tiles_x = cdiv(a.W, TWP); k.tiles_y = dd * cdiv(cdiv(a.H, dd), TR);
+    k.tile0 = L.ntiles;
+    k.ragged = !(a.W % 8 == 0 && k.xbs % 8 == 0 && k.gbs % 8 == 0 && aligned_to(a.x, 16) && aligned_to(a.grad_pre, 16));
+    L.ntiles += a.B * k.tiles_x * k.tiles_y;
   }
-  L.n = n; L.ntiles = t0;
-  const int nco2 = cdiv(Cout, 64 * MB), nci2 = cdiv(Cin, 64);
-  constexpr int lds_bytes = (G::X_BLOCKS + MB * G::G_BLOCKS) * 16;
-  static LdsOptIn opt;
-  auto kern = &wgrad_kernel<T, D, RAGGED, MB>;
-  opt.ensure(reinterpret_cast<const void*>(kern), lds_bytes);
-  hipLaunchKernelGGL(kern, dim3(ksplit * nco2 * nci2), dim3(NTHREADS * MB), lds_bytes, stream, L, ws, Cin, Cout, nci2, ksplit / 8);
+  L.n = n;
+  return L;
 }
-
-static bool level_ragged(const upf_wgrad_level& a, int Cin, int Cout) {
-  const long long xbs = a.x_batch_stride ? a.x_batch_stride : (long long)Cin * a.H * a.W;
-  const long long gbs = a.g_batch_stride ? a.g_batch_stride : (long long)Cout * a.H * a.W;
-  return !(a.W % 8 == 0 && xbs % 8 == 0 && gbs % 8 == 0 && aligned_to(a.x, 16) && aligned_to(a.grad_pre, 16));
-}
-static int level_tiles(const upf_wgrad_level& a, int dd) { return a.B * cdiv(a.W, TWP) * dd * cdiv(cdiv(a.H, dd), TR); }
 
 // More than 16 block pairs cannot run two tile lanes per XCD (32 CUs): a 567 -> 128 layer (18 pairs) would leave 14 of 32
 // CUs idle.  Its co blocks then go in separate launches (9 pairs, 3 lanes, 27 CUs per XCD); X is read once per launch.
 static bool pc_split_co(int nco2, int nci2) { return nco2 > 1 && nco2 * nci2 > 16 && nci2 <= 16; }
 
-template <typename T, int D, bool RAGGED>
-void launch_group_pc(const upf_wgrad_level* lv, const int* idx, int n, float* ws, int ns, int J, bool split_co, int Cin, int Cout, hipStream_t stream) {
-  using G = Geo<D>;
-  constexpr int DD = (D == 0) ? 1 : D;
-  KLevels L;
-  memset(&L, 0, sizeof(L));
-  int t0 = 0;
-  for (int i = 0; i < n; ++i) {
-    const upf_wgrad_level& a = lv[idx[i]];
-    KLevel& k = L.lv[i];
-    k.x = a.x; k.g = a.grad_pre;
-    k.xbs = a.x_batch_stride ? a.x_batch_stride : (long long)Cin * a.H * a.W;
-    k.gbs = a.g_batch_stride ? a.g_batch_stride : (long long)Cout * a.H * a.W;
-    k.H = a.H; k.W = a.W;
-    k.tiles_x = cdiv(a.W, TWP); k.tiles_y = DD * cdiv(cdiv(a.H, DD), TR);
-    k.tile0 = t0;
-    k.ragged = level_ragged(a, Cin, Cout) ? 1 : 0;
-    t0 += a.B * k.tiles_x * k.tiles_y;
-  }
-  L.n = n; L.ntiles = t0;
-  const int nco2 = cdiv(Cout, 64), nci2 = cdiv(Cin, 64);
-  constexpr int lds_bytes = 2 * (G::X_BLOCKS + G::G_BLOCKS) * 16 + MAXL * LT_STRIDE * 4;      // two staging buffers + the level table
-  static LdsOptIn opt;
-  auto kern = &wgrad_pc_kernel<T, D, RAGGED>;
-  opt.ensure(reinterpret_cast<const void*>(kern), lds_bytes);
-  static const int abl = [] { const char* e = getenv("UPF_WGRAD_ABLATE"); return e ? atoi(e) << 16 : 0; }();
-  const int ksplit = ns * J, J_ns = J | (ns << 16);
-  if (split_co) {                                // one launch per co block (see pc_split_co)
-    for (int c = 0; c < nco2; ++c)
-      hipLaunchKernelGGL(kern, dim3(ksplit * nci2), dim3(2 * NTHREADS), lds_bytes, stream, L, ws, Cin, Cout, nci2, J_ns, c | abl);
-  } else {
-    hipLaunchKernelGGL(kern, dim3(ksplit * nco2 * nci2), dim3(2 * NTHREADS), lds_bytes, stream, L, ws, Cin, Cout, nci2, J_ns, abl);
-  }
-}
-
-
-// The plan of one multi-level weight gradient.  Producer / consumer kernel (the default): ALL levels in one launch — one K
-// dimension, one set of partial blocks — with the shifted staging chosen per tile (`mixed`: some level is ragged).
-// wgrad_kernel (UPF_WGRAD_MODE=1, kept for A/B runs): aligned levels in one launch, ragged ones in a second, their K-splits
-// back to back in the workspace.  One reduction over all partial blocks either way.
-struct Plan {
-  int ia[MAXL], na = 0, ir[MAXL], nr = 0, ks_a = 0, ks_r = 0;
-  bool mixed = false;
-  int ns = 8, J = 1;                    // producer / consumer kernel: ks_a = ns * J
-  bool split_co = false;
-};
-
-// Producer / consumer kernel: how many slices of the tile range (ns) and workgroups per block pair and slice (J).  Every
-// workgroup ends by writing its 64 x 64 x taps fp32 block, which the reduction reads back: with the chip filled whatever the
+// How many slices of the tile range (ns) and workgroups per block pair and slice (J).  Every workgroup ends by writing its 64 x 64 x taps fp32 block, which the reduction reads back: with the chip filled whatever the
 // layer (round 4: ns = 8, J = 32 / block pairs) a 96 -> 96 layer at 16x52 — 64 tiles — wrote and re-read 38 MB for 1 GFLOP, and
 // the twelve single-level layers of the feature pyramid took 25-80 us each.  Cost model (us): tiles per workgroup x the
 // measured tile time + the partial blocks both ways at ~3.5 TB/s; UPF_WGRAD_SPLIT="ns,J" overrides (A/B runs).
@@ -1001,47 +725,56 @@ static void pick_split(int ntiles, int nb_launch, int nb_total, int ntaps, int& 
     }
   }
 }
-static Plan make_plan(const upf_wgrad_level* lv, int n, int Cin, int Cout, int kernel_size, int dilation) {
+
+// The plan of one multi-level weight gradient: ALL levels in one launch — one K dimension, one set of partial blocks — with the
+// shifted staging chosen per tile (`mixed`: some level is ragged); `split_co`: one launch per co block (see pc_split_co).
+struct Plan {
+  int ns = 8, J = 1;
+  bool split_co = false, mixed = false;
+};
+static Plan make_plan(const KLevels& L, int Cin, int Cout, int ntaps) {
   Plan p;
-  const int dd = kernel_size == 1 ? 1 : dilation, nt = kernel_size == 1 ? 1 : 9;
-  int ta = 0, tr = 0;
-  for (int i = 0; i < n; ++i) {
-    const bool rag = level_ragged(lv[i], Cin, Cout);
-    if (rag && wgrad_mode() != 0) { p.ir[p.nr++] = i; tr += level_tiles(lv[i], dd); }
-    else { p.ia[p.na++] = i; ta += level_tiles(lv[i], dd); p.mixed = p.mixed || rag; }
-  }
-  const int cob = co_block(Cout);
-  int nblocks = cdiv(Cout, cob) * cdiv(Cin, 64);
-  if (wgrad_mode() == 0) {
-    p.split_co = pc_split_co(cdiv(Cout, 64), cdiv(Cin, 64)) && ta >= 256;
-    pick_split(ta, p.split_co ? cdiv(Cin, 64) : nblocks, nblocks, nt, p.ns, p.J);
-    p.ks_a = p.ns * p.J;
-    return p;
-  }
-  if (p.na) p.ks_a = pick_ksplit(ta, nblocks, nt, cob);
-  if (p.nr) p.ks_r = pick_ksplit(tr, nblocks, nt, cob);
+  for (int i = 0; i < L.n; ++i) p.mixed = p.mixed || L.lv[i].ragged;
+  const int nco2 = cdiv(Cout, 64), nci2 = cdiv(Cin, 64);
+  p.split_co = pc_split_co(nco2, nci2) && L.ntiles >= 256;
+  pick_split(L.ntiles, p.split_co ? nci2 : nco2 * nci2, nco2 * nci2, ntaps, p.ns, p.J);
   return p;
 }
 
-template <typename T, int D>
-int run(const upf_wgrad_level* lv, int n, float* dw, float* ws, int Cin, int Cout, int kernel_size, int dilation, hipStream_t stream, int s2d = 0,
-        const BiasParts* bias = nullptr) {
+// The partial blocks of a plan, [ns * J][tap][pad64(Cout)][pad64(Cin)] fp32: how many K-split slots, and the workspace they take.
+struct Partials { int ksplit; long long bytes; };
+static Partials partials_of(const Plan& p, int ntaps, int Cin, int Cout) {
+  const int ksplit = p.ns * p.J;
+  return {ksplit, (long long)ksplit * ntaps * (cdiv(Cout, 64) * 64) * (cdiv(Cin, 64) * 64) * (long long)sizeof(float)};
+}
+
+template <typename T, int D, bool RAGGED>
+void launch(const KLevels& L, const Plan& p, float* ws, int Cin, int Cout, hipStream_t stream) {
   using G = Geo<D>;
-  const Plan p = make_plan(lv, n, Cin, Cout, kernel_size, dilation);
-  const int cob = co_block(Cout), cop = cdiv(Cout, cob) * cob;
-  const size_t per_split = (size_t)G::NT * cop * (cdiv(Cin, 64) * 64);
-  if (wgrad_mode() == 0) {
-    if (p.mixed) launch_group_pc<T, D, true>(lv, p.ia, p.na, ws, p.ns, p.J, p.split_co, Cin, Cout, stream);
-    else launch_group_pc<T, D, false>(lv, p.ia, p.na, ws, p.ns, p.J, p.split_co, Cin, Cout, stream);
-  } else if (cob == 128) {
-    if (p.na) launch_group<T, D, false, 2>(lv, p.ia, p.na, ws, p.ks_a, Cin, Cout, stream);
-    if (p.nr) launch_group<T, D, true, 2>(lv, p.ir, p.nr, ws + (size_t)p.ks_a * per_split, p.ks_r, Cin, Cout, stream);
+  const int nco2 = cdiv(Cout, 64), nci2 = cdiv(Cin, 64);
+  constexpr int lds_bytes = 2 * (G::X_BLOCKS + G::G_BLOCKS) * 16 + MAXL * LT_STRIDE * 4;      // two staging buffers + the level table
+  static LdsOptIn opt;
+  auto kern = &wgrad_pc_kernel<T, D, RAGGED>;
+  opt.ensure(reinterpret_cast<const void*>(kern), lds_bytes);
+  static const int abl = [] { const char* e = getenv("UPF_WGRAD_ABLATE"); return e ? atoi(e) << 16 : 0; }();
+  const int ksplit = p.ns * p.J, J_ns = p.J | (p.ns << 16);
+  if (p.split_co) {                              // one launch per co block (see pc_split_co)
+    for (int c = 0; c < nco2; ++c)
+      hipLaunchKernelGGL(kern, dim3(ksplit * nci2), dim3(2 * NTHREADS), lds_bytes, stream, L, ws, Cin, Cout, nci2, J_ns, c | abl);
   } else {
-    if (p.na) launch_group<T, D, false, 1>(lv, p.ia, p.na, ws, p.ks_a, Cin, Cout, stream);
-    if (p.nr) launch_group<T, D, true, 1>(lv, p.ir, p.nr, ws + (size_t)p.ks_a * per_split, p.ks_r, Cin, Cout, stream);
+    hipLaunchKernelGGL(kern, dim3(ksplit * nco2 * nci2), dim3(2 * NTHREADS), lds_bytes, stream, L, ws, Cin, Cout, nci2, J_ns, abl);
   }
+}
+
+template <typename T, int D>
+int run(const upf_wgrad_level* lv, int n, float* dw, float* ws, int Cin, int Cout, hipStream_t stream, int s2d = 0, const BiasParts* bias = nullptr) {
+  using G = Geo<D>;
+  const KLevels L = make_levels(lv, n, Cin, Cout, D);
+  const Plan p = make_plan(L, Cin, Cout, G::NT);
+  if (p.mixed) launch<T, D, true>(L, p, ws, Cin, Cout, stream);
+  else launch<T, D, false>(L, p, ws, Cin, Cout, stream);
+  const int ks = partials_of(p, G::NT, Cin, Cout).ksplit, cop = cdiv(Cout, 64) * 64;
   const long long items = (long long)Cout * cdiv(Cin, 4);
-  const int ks = p.ks_a + p.ks_r;
   BiasParts BP;
   memset(&BP, 0, sizeof(BP));
   if (bias) BP = *bias;
@@ -1083,9 +816,8 @@ extern "C" long long upf_conv_wgrad_multi_workspace_bytes(const upf_wgrad_level*
   using namespace upf;
   if (!levels || nlevels < 1 || nlevels > wgrad::MAXL) return -1;
   const int nt = kernel_size == 1 ? 1 : 9;
-  const wgrad::Plan p = wgrad::make_plan(levels, nlevels, Cin, Cout, kernel_size, kernel_size == 1 ? 1 : dilation);
-  const int cob = wgrad::co_block(Cout);
-  return (long long)(p.ks_a + p.ks_r) * nt * (cdiv(Cout, cob) * cob) * (cdiv(Cin, 64) * 64) * (long long)sizeof(float);
+  const wgrad::KLevels L = wgrad::make_levels(levels, nlevels, Cin, Cout, kernel_size == 1 ? 0 : dilation);
+  return wgrad::partials_of(wgrad::make_plan(L, Cin, Cout, nt), nt, Cin, Cout).bytes;
 }
 
 extern "C" int upf_conv_wgrad_multi_bias(const upf_wgrad_level* levels, int nlevels, float* grad_w, void* workspace, int Cin, int Cout,
@@ -1107,8 +839,8 @@ extern "C" int upf_conv_wgrad_multi_bias(const upf_wgrad_level* levels, int nlev
   const wgrad::BiasParts* bp = npartials ? &BP : nullptr;
   hipStream_t s = (hipStream_t)stream;
   const int D = kernel_size == 1 ? 0 : dilation;
-#define UPF_WG(DV) case DV: return dtype == UPF_BF16 ? wgrad::run<bf16_t, DV>(levels, nlevels, grad_w, (float*)workspace, Cin, Cout, kernel_size, dilation, s, 0, bp) \
-                                                     : wgrad::run<f16_t, DV>(levels, nlevels, grad_w, (float*)workspace, Cin, Cout, kernel_size, dilation, s, 0, bp);
+#define UPF_WG(DV) case DV: return dtype == UPF_BF16 ? wgrad::run<bf16_t, DV>(levels, nlevels, grad_w, (float*)workspace, Cin, Cout, s, 0, bp) \
+                                                     : wgrad::run<f16_t, DV>(levels, nlevels, grad_w, (float*)workspace, Cin, Cout, s, 0, bp);
   switch (D) {
     UPF_WG(0) UPF_WG(1) UPF_WG(2) UPF_WG(4) UPF_WG(8) UPF_WG(16)
   }
@@ -1127,8 +859,8 @@ extern "C" int upf_conv_wgrad_s2d(const upf_wgrad_level* levels, int nlevels, fl
   UPF_REQUIRE(grad_w && workspace, UPF_EINVAL, "conv_wgrad_s2d: null pointer");
   if (int rc = wgrad_check_levels(levels, nlevels, 4 * Cin, Cout, 3, 1, dtype)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  return dtype == UPF_BF16 ? wgrad::run<bf16_t, 1>(levels, nlevels, grad_w, (float*)workspace, 4 * Cin, Cout, 3, 1, s, 1)
-                           : wgrad::run<f16_t, 1>(levels, nlevels, grad_w, (float*)workspace, 4 * Cin, Cout, 3, 1, s, 1);
+  return dtype == UPF_BF16 ? wgrad::run<bf16_t, 1>(levels, nlevels, grad_w, (float*)workspace, 4 * Cin, Cout, s, 1)
+                           : wgrad::run<f16_t, 1>(levels, nlevels, grad_w, (float*)workspace, 4 * Cin, Cout, s, 1);
 }
 
 extern "C" long long upf_conv_wgrad_workspace_bytes(int B, int Cin, int Cout, int H, int W, int kernel_size, int dilation) {
