@@ -526,7 +526,7 @@ def shared_case(dtype):
 CORR_GRIDS = {torch.bfloat16: {'f': (0.125, 2.0), 'g': (0.25, 2.0)}, torch.float16: {'f': (2.0 ** -5, 2.0), 'g': (2.0 ** -4, 2.0)}}
 CORR_R, CORR_D, CORR_ND = 4, 9, 81
 
-# Shapes (B, C, H, W), sized on the dispatch code (launch_fwd / try_allc / allc_pick in csrc/corr81_fwd.hip, upf_corr81_backward in
+# Shapes (B, C, H, W), sized on the dispatch code (route() in csrc/corr81_fwd.hip, upf_corr81_backward in
 # csrc/corr81_bwd.hip): H = 9 / 5 / 6 is no multiple of a tile height (8, 4, 2), W = 40 / 35 crosses the 32- and 16-pixel tiles.
 CORR_C = (5, 32, 96, 196, 208)
 CORR_ALLC = [(2 if C == 32 else 1, C, 9, W) for W in (40, 35) for C in CORR_C]                # aligned and ragged rows; one B = 2 each

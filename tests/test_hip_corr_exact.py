@@ -15,7 +15,7 @@ order (_exact_model.slope01_ref).  Values are compared as values (signed zeros a
 Every operand is a contiguous block of a NaN-filled arena and so is every output an entry point lets the caller pass: whatever a
 kernel reads outside its operands is NaN, whatever it writes outside its output shows in `untouched`.
 
-Routes (what selects each is read off launch_fwd / try_allc / allc_pick and upf_corr81_backward):
+Routes (what selects each is read off route() in csrc/corr81_fwd.hip and upf_corr81_backward):
   all-channels kernel, geometry 0..3 (8x32, 4x32, 2x32, 4x16 tiles)   corr_set_option('variant', v) where C fits, else the default pick
     aligned form: W % 8 == 0, 16-byte aligned f1 / f2 / out, out_batch_stride % 8 == 0; ragged form: anything else with W >= 4
   MFMA kernel   old_path = 1 on the aligned form's conditions (one chunk: C <= 32); no option: C > 208, or C > 40 on >= 160 8x32 tiles
@@ -150,7 +150,7 @@ def test_forward_beyond_the_all_channels_kernel(shape, dtype):
 
 @pytest.mark.parametrize('dtype', DT)
 def test_forward_many_tiles_route(dtype):
-    """C > 40 on >= 160 8x32 tiles (allc_pick's -2): the MFMA kernel by default; (8, 48, 40, 128) is the smallest such grid."""
+    """C > 40 on >= 160 8x32 tiles (route() leaves these to the chunked kernels): the MFMA kernel by default; (8, 48, 40, 128) is the smallest such grid."""
     B, C, H, W = em.CORR_BIG
     assert C > 40 and B * -(-H // 8) * -(-W // 32) >= 160
     forward_case(em.CORR_BIG, dtype)

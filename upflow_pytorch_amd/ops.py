@@ -87,26 +87,49 @@ def _out_pitch_or_raise(t, what):
 # ------------------------------------------------------------------------------------------------
 # cost volume
 # ------------------------------------------------------------------------------------------------
+def _corr_pair(f1, f2, who):
+    """(B, C, H, W) of the two feature tensors of a cost volume: one shape, one dtype."""
+    if f1.shape != f2.shape or f1.dim() != 4 or f1.dtype != f2.dtype:
+        raise UpflowHipError('%s: inputs must be two [B,C,H,W] tensors of one dtype, got %s %s / %s %s'
+                             % (who, tuple(f1.shape), f1.dtype, tuple(f2.shape), f2.dtype))
+    return f1.shape
+
+
+def _corr_out(out, f1, dtypes, who):
+    """-> (out, batch stride for the entry point): a fresh [B,81,H,W] tensor (stride 0 = contiguous) for None, else `out` checked to
+    be a [B,81,H,W] channel slice of a contiguous NCHW buffer of one of `dtypes`."""
+    B, C, H, W = f1.shape
+    if out is None:
+        return torch.empty((B, 81, H, W), dtype=f1.dtype, device=f1.device), 0
+    if out.shape != (B, 81, H, W) or out.dtype not in dtypes or out.device != f1.device:
+        raise UpflowHipError('%s: bad `out` %s %s' % (who, tuple(out.shape), out.dtype))
+    if out.stride()[1:] != (H * W, W, 1):
+        raise UpflowHipError('%s: `out` must be a channel slice of a contiguous NCHW buffer' % who)
+    return out, out.stride(0)
+
+
+def _corr_norm_workspace(f):
+    """Scratch of the normalising cost volume's statistics launch (upf_corr81_norm_workspace_bytes)."""
+    return torch.empty((_lib.lib().upf_corr81_norm_workspace_bytes(*f.shape),), dtype=torch.uint8, device=f.device)
+
+
+def _timed_call(dev, name, nrep, *args):
+    """-> (avg_us, min_us) of a *_timed entry point: `args`, then the current stream of `dev`, `nrep` and the two results."""
+    import ctypes
+    avg, mn = ctypes.c_float(), ctypes.c_float()
+    with torch.cuda.device(dev):
+        _lib.call(name, *args, _lib.stream_ptr(dev), int(nrep), ctypes.byref(avg), ctypes.byref(mn))
+    return avg.value, mn.value
+
+
 def corr81_forward_raw(f1, f2, out=None, leaky_slope=0.0):
     """One launch of upf_corr81_forward.  `out` may be a [B,81,H,W] channel-slice of a wider
     contiguous [B,Ctot,H,W] buffer (e.g. the 115-channel estimator input, model/upflow.py:565)."""
-    if f1.shape != f2.shape or f1.dim() != 4 or f1.dtype != f2.dtype:
-        raise UpflowHipError('corr81: inputs must be two [B,C,H,W] tensors of one dtype, got %s %s / %s %s'
-                             % (tuple(f1.shape), f1.dtype, tuple(f2.shape), f2.dtype))
-    B, C, H, W = f1.shape
+    B, C, H, W = _corr_pair(f1, f2, 'corr81')
     dev = _lib.check_gpu(f1, f2)
-    if out is None:
-        out = torch.empty((B, 81, H, W), dtype=f1.dtype, device=f1.device)
-        bstride = 0
-    else:
-        if out.shape != (B, 81, H, W) or out.dtype != f1.dtype or out.device != f1.device:
-            raise UpflowHipError('corr81: bad `out` %s %s' % (tuple(out.shape), out.dtype))
-        if out.stride()[1:] != (H * W, W, 1):
-            raise UpflowHipError('corr81: `out` must be a channel slice of a contiguous NCHW buffer')
-        bstride = out.stride(0)
-    with torch.cuda.device(dev):
-        _lib.call('upf_corr81_forward', _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(out), B, C, H, W,
-                  _lib.dtype_code(f1), bstride, float(leaky_slope), _lib.stream_ptr(dev))
+    out, bstride = _corr_out(out, f1, (f1.dtype,), 'corr81')
+    _lib.launch(dev, 'upf_corr81_forward', _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(out), B, C, H, W,
+                _lib.dtype_code(f1), bstride, float(leaky_slope))
     return out
 
 
@@ -129,26 +152,14 @@ def corr81_norm_forward_raw(f1, f2, out=None, leaky_slope=0.0):
     """corr81(normalize(f1), normalize(f2)) with the normalisation applied inside the cost volume's loader
     (upf_corr81_norm_forward: one statistics launch + one cost-volume launch; bit-identical to normalize x2 + corr81).
     Inference only.  `out` as in corr81_forward_raw."""
-    if f1.shape != f2.shape or f1.dim() != 4 or f1.dtype != f2.dtype:
-        raise UpflowHipError('corr81_norm: inputs must be two [B,C,H,W] tensors of one dtype, got %s %s / %s %s'
-                             % (tuple(f1.shape), f1.dtype, tuple(f2.shape), f2.dtype))
-    B, C, H, W = f1.shape
+    B, C, H, W = _corr_pair(f1, f2, 'corr81_norm')
     dev = _lib.check_gpu(f1, f2, contiguous=False)
     fp = _feature_pair_pitch(f1, f2, 'corr81_norm')
-    if out is None:
-        out = torch.empty((B, 81, H, W), dtype=f1.dtype, device=f1.device)
-        bstride = 0
-    else:
-        # (`out` may be the OTHER 16-bit type: fp16 pyramid features into a bf16 estimator buffer, the `pyramid_dtype` option)
-        if out.shape != (B, 81, H, W) or out.dtype not in (torch.bfloat16, torch.float16) or out.device != f1.device:
-            raise UpflowHipError('corr81_norm: bad `out` %s %s' % (tuple(out.shape), out.dtype))
-        if out.stride()[1:] != (H * W, W, 1):
-            raise UpflowHipError('corr81_norm: `out` must be a channel slice of a contiguous NCHW buffer')
-        bstride = out.stride(0)
-    ws = torch.empty((_lib.lib().upf_corr81_norm_workspace_bytes(B, C, H, W),), dtype=torch.uint8, device=f1.device)
-    with torch.cuda.device(dev):
-        _lib.call('upf_corr81_norm_forward_mixed', _lib.ptr(f1), _lib.ptr(f2), fp, _lib.ptr(out), B, C, H, W,
-                  _lib.dtype_code(f1), _lib.dtype_code(out), bstride, float(leaky_slope), _lib.ptr(ws), _lib.stream_ptr(dev))
+    # (`out` may be the OTHER 16-bit type: fp16 pyramid features into a bf16 estimator buffer, the `pyramid_dtype` option)
+    out, bstride = _corr_out(out, f1, (torch.bfloat16, torch.float16), 'corr81_norm')
+    ws = _corr_norm_workspace(f1)
+    _lib.launch(dev, 'upf_corr81_norm_forward_mixed', _lib.ptr(f1), _lib.ptr(f2), fp, _lib.ptr(out), B, C, H, W,
+                _lib.dtype_code(f1), _lib.dtype_code(out), bstride, float(leaky_slope), _lib.ptr(ws))
     return out
 
 
@@ -178,19 +189,16 @@ def corr81_c8_channel_map():
 
 def corr81_norm_forward_c8(f1, f2, out8, leaky_slope=0.0):
     """corr81_norm_forward_raw into 11 octets `out8` [B,11,H,W,8] of a channel-octet buffer (order: corr81_c8_channel_map)."""
-    if f1.shape != f2.shape or f1.dim() != 4 or f1.dtype != f2.dtype:
-        raise UpflowHipError('corr81_norm_c8: inputs must be two [B,C,H,W] tensors of one dtype')
-    B, C, H, W = f1.shape
+    B, C, H, W = _corr_pair(f1, f2, 'corr81_norm_c8')
     dev = _lib.check_gpu(f1, f2, contiguous=False)
     if not out8.is_cuda or tuple(out8.shape) != (B, CORR81_C8_OCTETS, H, W, 8) or not _c8_view_ok(out8) or out8.dtype not in (torch.bfloat16, torch.float16):
         raise UpflowHipError('corr81_norm_c8: out8 must be an octet slice [%d,11,%d,%d,8] of a 16-bit C8 buffer, got %s' % (B, H, W, tuple(out8.shape)))
     if nchw_pitch(f1) is None or nchw_pitch(f2) is None:
         f1, f2 = f1.contiguous(), f2.contiguous()
     fp = _feature_pair_pitch(f1, f2, 'corr81_norm_c8')
-    ws = torch.empty((_lib.lib().upf_corr81_norm_workspace_bytes(B, C, H, W),), dtype=torch.uint8, device=f1.device)
-    with torch.cuda.device(dev):
-        _lib.call('upf_corr81_norm_forward_c8_mixed', _lib.ptr(f1), _lib.ptr(f2), fp, _lib.ptr(out8), out8.stride(0), B, C, H, W,
-                  _lib.dtype_code(f1), _lib.dtype_code(out8), float(leaky_slope), _lib.ptr(ws), _lib.stream_ptr(dev))
+    ws = _corr_norm_workspace(f1)
+    _lib.launch(dev, 'upf_corr81_norm_forward_c8_mixed', _lib.ptr(f1), _lib.ptr(f2), fp, _lib.ptr(out8), out8.stride(0), B, C, H, W,
+                _lib.dtype_code(f1), _lib.dtype_code(out8), float(leaky_slope), _lib.ptr(ws))
     return out8
 
 
@@ -215,49 +223,34 @@ def flow_update_c8(a, b, c, out8):
 def corr81_forward_timed(f1, f2, out, leaky_slope=0.0, nrep=50):
     """-> (avg_us, min_us) of `nrep` launches, each timed by HIP events recorded around the kernel on
     the current stream (upf_corr81_forward_timed).  Measurement helper for bench.py."""
-    import ctypes
     B, C, H, W = f1.shape
     dev = _lib.check_gpu(f1, f2, out)
-    avg, mn = ctypes.c_float(), ctypes.c_float()
-    with torch.cuda.device(dev):
-        _lib.call('upf_corr81_forward_timed', _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(out), B, C, H, W,
-                  _lib.dtype_code(f1), 0, float(leaky_slope), _lib.stream_ptr(dev), int(nrep),
-                  ctypes.byref(avg), ctypes.byref(mn))
-    return avg.value, mn.value
+    return _timed_call(dev, 'upf_corr81_forward_timed', nrep, _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(out), B, C, H, W,
+                       _lib.dtype_code(f1), 0, float(leaky_slope))
 
 
 def corr81_norm_forward_timed(f1, f2, out, leaky_slope=0.0, nrep=50):
     """-> (avg_us, min_us) of `nrep` launches of the NORMALISING cost volume (the kernel inside the inference step), each
     between its own pair of HIP events; the statistics launch runs once, untimed.  Measurement helper for bench.py."""
-    import ctypes
     B, C, H, W = f1.shape
     dev = _lib.check_gpu(f1, f2, out)
-    ws = torch.empty((_lib.lib().upf_corr81_norm_workspace_bytes(B, C, H, W),), dtype=torch.uint8, device=f1.device)
-    avg, mn = ctypes.c_float(), ctypes.c_float()
-    with torch.cuda.device(dev):
-        _lib.call('upf_corr81_norm_forward_timed', _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(out), B, C, H, W,
-                  _lib.dtype_code(f1), 0, float(leaky_slope), _lib.ptr(ws), _lib.stream_ptr(dev), int(nrep),
-                  ctypes.byref(avg), ctypes.byref(mn))
-    return avg.value, mn.value
+    ws = _corr_norm_workspace(f1)
+    return _timed_call(dev, 'upf_corr81_norm_forward_timed', nrep, _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(out), B, C, H, W,
+                       _lib.dtype_code(f1), 0, float(leaky_slope), _lib.ptr(ws))
 
 
 def corr81_norm_forward_c8_timed(f1, f2, out8, leaky_slope=0.0, nrep=50):
     """corr81_norm_forward_timed for the octet-output form (corr81_norm_forward_c8): the launch inside the inference step at
     the levels whose flow estimator runs in the channel-octet layout."""
-    import ctypes
     B, C, H, W = f1.shape
     dev = _lib.check_gpu(f1, f2, contiguous=False)
     if tuple(out8.shape) != (B, CORR81_C8_OCTETS, H, W, 8) or not _c8_view_ok(out8):
         raise UpflowHipError('corr81_norm_c8_timed: out8 must be an octet slice [%d,11,%d,%d,8]' % (B, H, W))
     fp = _feature_pair_pitch(f1, f2, 'corr81_norm_c8_timed')
-    ws = torch.empty((_lib.lib().upf_corr81_norm_workspace_bytes(B, C, H, W),), dtype=torch.uint8, device=f1.device)
-    avg, mn = ctypes.c_float(), ctypes.c_float()
-    with torch.cuda.device(dev):
-        # (out8 may be the OTHER 16-bit type: fp16 features into bf16 octets — the launch of the bf16 step with its fp16 pyramid)
-        _lib.call('upf_corr81_norm_forward_c8_timed_mixed', _lib.ptr(f1), _lib.ptr(f2), fp, _lib.ptr(out8), out8.stride(0), B, C, H, W,
-                  _lib.dtype_code(f1), _lib.dtype_code(out8), float(leaky_slope), _lib.ptr(ws), _lib.stream_ptr(dev), int(nrep),
-                  ctypes.byref(avg), ctypes.byref(mn))
-    return avg.value, mn.value
+    ws = _corr_norm_workspace(f1)
+    # (out8 may be the OTHER 16-bit type: fp16 features into bf16 octets — the launch of the bf16 step with its fp16 pyramid)
+    return _timed_call(dev, 'upf_corr81_norm_forward_c8_timed_mixed', nrep, _lib.ptr(f1), _lib.ptr(f2), fp, _lib.ptr(out8), out8.stride(0),
+                       B, C, H, W, _lib.dtype_code(f1), _lib.dtype_code(out8), float(leaky_slope), _lib.ptr(ws))
 
 
 def corr81_backward_raw(f1, f2, grad_out, g1=None, g2=None):
