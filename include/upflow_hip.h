@@ -716,6 +716,23 @@ int upf_adam_amsgrad_step(const upf_mt_launch* launch, const float* lr, const fl
 int upf_loss_scale_update(float* loss_scale, int* growth_tracker, int* skipped_steps, int* flag, float* steps, int nsteps,
                           float growth_factor, float backoff_factor, int growth_interval, void* stream);
 
+/* ---- batch assembly from uint8 frames ----------------------------------------------------------------------------------------
+ * The host data path of the reference (dataset/kitti_dataset.py:62-80, 268-342: img_func.get_process_img_only_img — flip,
+ * (image - mean) / stddev in float64, HWC -> CHW — then kitti_data_with_start_point.random_crop and the fp32 conversion) as ONE
+ * launch:
+ *   raw[b,c,y,x]  = (float)(((double)src[b, y, flip_b ? W-1-x : x, c] - mean_c) / stddev)     IEEE double, one rounding to fp32
+ *   crop[b,c,i,j] = raw[b,c,y_b+i,x_b+j]            start[b] = (x_b, y_b)
+ * src1 / src2 uint8 [B,H,W,3] contiguous (src2 may be NULL: one frame set; raw2 / crop2 are then ignored); raw1 / raw2 fp32
+ * [B,3,H,W]; crop1 / crop2 fp32 [B,3,ph,pw] (ph = pw = 0: no crops, the pointers are ignored); start fp32 [B,2] or NULL.
+ * aug int32 [B,3] = (x, y, flip) in DEVICE memory, read by the kernel (NULL: all zero): x is clamped to [0, W-pw], y to
+ * [0, H-ph], flip is `!= 0`, and start reports the clamped values — no value of aug makes the kernel leave src or the outputs.
+ * mean = 0,0,0 and stddev = 1 give the un-normalised frames (normalize=False).  Every source byte is read once; the frame and
+ * its crop are written from the same pass.  UPF_EINVAL: non-positive sizes, a crop larger than the frame, null src1 / outputs;
+ * UPF_EUNSUPPORTED: a batch item of 2 GiB or more. */
+int upf_frames_u8_assemble(const unsigned char* src1, const unsigned char* src2, const int* aug, float* raw1, float* raw2,
+                           float* crop1, float* crop2, float* start, int B, int H, int W, int ph, int pw,
+                           double mean0, double mean1, double mean2, double stddev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

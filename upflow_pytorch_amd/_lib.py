@@ -109,6 +109,7 @@ SIGNATURES = {
     'upf_grads_nonfinite_check': [_vp, _vp, _vp],
     'upf_adam_amsgrad_step': [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp],
     'upf_loss_scale_update': [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp],
+    'upf_frames_u8_assemble': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp],
 }
 
 

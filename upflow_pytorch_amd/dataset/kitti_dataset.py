@@ -140,6 +140,27 @@ class kitti_train:
                 return im2, im1
             return im1, im2
 
+    class kitti_data_u8(kitti_data_with_start_point):
+        """The same samples as undecoded work: `(frame1 uint8 [H,W,3], frame2 uint8 [H,W,3], aug int32 [3] = (x, y, flip))`.
+        No float arithmetic, no flipped copy, no crop on the host — ops.assemble_train_batch does all three on the device
+        (Trainer.step takes the collated batch as {'frames1_u8', 'frames2_u8', 'aug', 'crop_size'}).  The random draws are the
+        parent's, in its order and under its conditions — flip (only with horizontal_flip_aug), swap (only with swap_images), x,
+        y — so with equal seeds the two classes describe the same sample.  The config class is the parent's (whose __call__
+        builds the parent): `kitti_train.kitti_data_u8(conf)`.  (Not in the reference.)"""
+
+        def __getitem__(self, index):
+            flip = bool(self.conf.horizontal_flip_aug and random.random() < 0.5)
+            p1, p2 = self.filenames_extended[index % self.N]
+            im1, im2 = flow_io.read_image(p1), flow_io.read_image(p2)
+            if self.conf.swap_images and random.random() < 0.5:
+                im1, im2 = im2, im1                                       # (the swap is the order of the returned frames)
+            height, width = im1.shape[:2]
+            ph, pw = self.conf.crop_size
+            x = np.random.randint(self.conf.rho, width - self.conf.rho - pw)
+            y = np.random.randint(self.conf.rho, height - self.conf.rho - ph)
+            aug = torch.tensor([x, y, int(flip)], dtype=torch.int32)
+            return torch.from_numpy(np.ascontiguousarray(im1)), torch.from_numpy(np.ascontiguousarray(im2)), aug
+
 
 class kitti_flow:
     @classmethod
@@ -157,17 +178,27 @@ class kitti_flow:
         return data
 
     class kitti_train():
-        def __init__(self, name, root=None):
+        def __init__(self, name, root=None, u8=False):
+            """u8=True: im1 / im2 come back as the decoded uint8 [H,W,3] frames — Test_model.eval_forward normalises them on the
+            device (ops.frames_from_u8), bit for bit what the default item holds; flows and masks are unchanged."""
             assert name in ['2012_train', '2015_train', '2012_test', '2015_test']
             self.file_names = kitti_flow.get_file_names(root)[name]
             self.normalize = True
             self.name = name
+            self.u8 = bool(u8)
 
         def __len__(self):
             return len(self.file_names)
 
         def __getitem__(self, index):
             d = self.file_names[index]
+            if self.u8:
+                frames = [torch.from_numpy(np.ascontiguousarray(flow_io.read_image(d[k]))) for k in ('im1', 'im2')]
+                if self.name.endswith('_test'):
+                    return frames[0], frames[1], os.path.basename(d['im1']).replace('.png', '')
+                occ, occmask = img_func.read_png_flow(d['flow_occ'])
+                noc, nocmask = img_func.read_png_flow(d['flow_noc'])
+                return tuple(frames + img_func.np_2_tensor(occ, occmask, noc, nocmask))
             im1 = img_func.get_process_img(d['im1'], normalize=self.normalize)
             im2 = img_func.get_process_img(d['im2'], normalize=self.normalize)
             if self.name.endswith('_test'):

@@ -2534,3 +2534,82 @@ def loss_scale_update(loss_scale, growth_tracker, skipped_steps, flag, steps, gr
               _mt_scalar(growth_tracker, torch.int32, 'growth_tracker'), _mt_scalar(skipped_steps, torch.int32, 'skipped_steps'),
               _mt_scalar(flag, torch.int32, 'flag'), _mt_scalar(steps, torch.float32, 'steps'), int(steps.numel()),
               float(growth_factor), float(backoff_factor), int(growth_interval), _lib.stream_ptr(loss_scale.device))
+
+
+# ---- batch assembly from uint8 frames (csrc/ingest.hip) -----------------------------------------------------------------------
+def _ingest_constants(normalize):
+    """(mean0, mean1, mean2, stddev) of the host data path — img_func is the one source of truth; normalize=False: 0, 0, 0, 1."""
+    if not normalize:
+        return 0.0, 0.0, 0.0, 1.0
+    from .dataset.kitti_dataset import img_func
+    return float(img_func.MEAN[0]), float(img_func.MEAN[1]), float(img_func.MEAN[2]), float(img_func.STDDEV)
+
+
+def _u8_frames(name, t, like=None):
+    if not (torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] == 3):
+        raise UpflowHipError('%s: uint8 frames [B,H,W,3] expected, got %s' % (name, (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t)))
+    if like is not None and t.shape != like.shape:
+        raise UpflowHipError('%s: the two frame sets differ in shape: %s vs %s' % (name, tuple(like.shape), tuple(t.shape)))
+    return t
+
+
+def check_aug(aug, H, W, crop_size):
+    """Host-side range check of a CPU `aug` [B,3] = (x, y, flip): 0 <= x <= W-pw, 0 <= y <= H-ph, else ValueError (nothing is
+    clamped silently; a DEVICE aug cannot be looked at without a synchronisation — the kernel clamps it)."""
+    ph, pw = int(crop_size[0]), int(crop_size[1])
+    if not (0 < ph <= H and 0 < pw <= W):
+        raise ValueError('crop_size %r does not fit the %d x %d frames' % (tuple(crop_size), H, W))
+    if aug.dim() != 2 or aug.shape[1] != 3 or aug.dtype not in (torch.int32, torch.int64):
+        raise ValueError('aug: an integer tensor [B,3] = (x, y, flip) expected, got %s %s' % (tuple(aug.shape), aug.dtype))
+    if not aug.is_cuda and aug.numel():
+        x, y = aug[:, 0], aug[:, 1]
+        if int(x.min()) < 0 or int(x.max()) > W - pw or int(y.min()) < 0 or int(y.max()) > H - ph:
+            raise ValueError('aug: crop origin outside 0 <= x <= %d, 0 <= y <= %d (x in [%d, %d], y in [%d, %d])'
+                             % (W - pw, H - ph, int(x.min()), int(x.max()), int(y.min()), int(y.max())))
+
+
+def _frames_u8_assemble(name, f1, f2, aug, ph, pw, normalize, want_start):
+    dev = _lib.check_gpu(f1, f2, aug)
+    B, H, W, _ = f1.shape
+    if aug is not None and (aug.dtype != torch.int32 or tuple(aug.shape) != (B, 3)):
+        raise UpflowHipError('%s: aug must be int32 [%d,3], got %s %s' % (name, B, tuple(aug.shape), aug.dtype))
+    if not (0 <= ph <= H and 0 <= pw <= W and (ph > 0) == (pw > 0)):
+        raise UpflowHipError('%s: crop %d x %d does not fit the %d x %d frames' % (name, ph, pw, H, W))
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=f1.device)   # noqa: E731
+    raw1, raw2 = new(B, 3, H, W), (new(B, 3, H, W) if f2 is not None else None)
+    crop1 = new(B, 3, ph, pw) if ph else None
+    crop2 = new(B, 3, ph, pw) if ph and f2 is not None else None
+    start = new(B, 2, 1, 1) if want_start else None
+    _lib.launch(dev, 'upf_frames_u8_assemble', _lib.ptr(f1), _lib.ptr(f2), _lib.ptr(aug), _lib.ptr(raw1), _lib.ptr(raw2),
+                _lib.ptr(crop1), _lib.ptr(crop2), _lib.ptr(start), B, H, W, ph, pw, *_ingest_constants(normalize))
+    return raw1, raw2, crop1, crop2, start
+
+
+def frames_from_u8(u8, flip=None, normalize=True):
+    """uint8 frames [B,H,W,3] -> fp32 [B,3,H,W], the bits of img_func.get_process_img_only_img + np_2_tensor
+    (dataset/kitti_dataset.py:62-80): (u8 - MEAN) / STDDEV in float64 rounded once to fp32, transposed; one launch.
+    flip: optional int32 device tensor [B], != 0 mirrors that item horizontally."""
+    _u8_frames('frames_from_u8', u8)
+    _lib.check_gpu(u8, flip)
+    aug = None
+    if flip is not None:
+        if flip.dtype != torch.int32 or tuple(flip.shape) != (u8.shape[0],):
+            raise UpflowHipError('frames_from_u8: flip must be int32 [%d], got %s %s' % (u8.shape[0], tuple(flip.shape), flip.dtype))
+        aug = torch.zeros((u8.shape[0], 3), dtype=torch.int32, device=u8.device)
+        aug[:, 2] = flip
+    return _frames_u8_assemble('frames_from_u8', u8, None, aug, 0, 0, normalize, False)[0]
+
+
+def assemble_train_batch(frames1_u8, frames2_u8, aug, crop_size, normalize=True):
+    """The training batch of kitti_data_with_start_point (dataset/kitti_dataset.py:268-342; train.synthetic_train_batch has the
+    same keys) from uint8 frames [B,H,W,3] and aug int32 [B,3] = (x, y, flip), in ONE launch that reads aug on the device:
+    {'im1', 'im2': the crops [B,3,ph,pw]; 'im1_raw', 'im2_raw' [B,3,H,W]; 'start' [B,2,1,1] = (x, y)}, bit for bit the host path's
+    tensors.  A CPU aug is range-checked here (ValueError) and uploaded; a device aug is clamped by the kernel."""
+    _u8_frames('assemble_train_batch', frames1_u8)
+    _u8_frames('assemble_train_batch', frames2_u8, like=frames1_u8)
+    ph, pw = int(crop_size[0]), int(crop_size[1])
+    check_aug(aug, frames1_u8.shape[1], frames1_u8.shape[2], (ph, pw))
+    _lib.check_gpu(frames1_u8, frames2_u8)
+    aug = aug.to(device=frames1_u8.device, dtype=torch.int32, non_blocking=True).contiguous()
+    raw1, raw2, crop1, crop2, start = _frames_u8_assemble('assemble_train_batch', frames1_u8, frames2_u8, aug, ph, pw, normalize, True)
+    return {'im1': crop1, 'im2': crop2, 'im1_raw': raw1, 'im2_raw': raw2, 'start': start}

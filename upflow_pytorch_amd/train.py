@@ -158,8 +158,31 @@ class Trainer():
         idx = parallel.shard_indices(n, self.rank, self.world)
         return {k: (v[idx] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == n else v) for k, v in batch.items()}
 
+    U8_KEYS = ('frames1_u8', 'frames2_u8', 'aug', 'crop_size')
+
+    def _u8_inputs(self, batch):
+        """A uint8 batch {'frames1_u8', 'frames2_u8' [B,H,W,3], 'aug' int32 [B,3] = (x, y, flip), 'crop_size': (ph, pw)} — what
+        dataset.kitti_train.kitti_data_u8 collates to — with its three tensors on the trainer's device: they are what the step
+        (and, captured, its static inputs) reads.  A CPU aug is range-checked here, before the upload (ValueError); the
+        frames' own checks are ops.assemble_train_batch's."""
+        from . import ops
+        f1, aug = batch['frames1_u8'], batch['aug']
+        ops.check_aug(aug, f1.shape[1], f1.shape[2], batch['crop_size'])
+        batch = dict(batch)
+        batch['crop_size'] = tuple(int(v) for v in batch['crop_size'])
+        batch['aug'] = aug.to(torch.int32)
+        if self.device is not None:
+            for k in ('frames1_u8', 'frames2_u8', 'aug'):
+                batch[k] = batch[k].to(device=self.device, non_blocking=True)
+        return batch
+
     def _step_body(self, batch):
         batch = dict(batch)
+        if 'frames1_u8' in batch:
+            # the crop, flip, normalisation and transpose as the step's FIRST launch (captured with it: a replay reads the new
+            # frames and aug from the static inputs); the network is handed the five fp32 tensors of the host data path
+            from . import ops
+            batch.update(ops.assemble_train_batch(*[batch.pop(k) for k in self.U8_KEYS]))
         batch['if_loss'] = True
         out = self.net(batch)
         loss, parts = self.loss_manager.compute_loss(out)
@@ -216,6 +239,8 @@ class Trainer():
         """One optimisation step on this rank's shard; returns the loss terms averaged over ranks
         (sync_stats=False: the device tensor of the terms, no host synchronisation)."""
         self.net.train()
+        if 'frames1_u8' in batch:            # (a batch without the uint8 keys takes the path below untouched)
+            batch = self._u8_inputs(batch)
         if self.use_graph and self._graph is not None and not self._replay_agreed(batch):
             import warnings
             warnings.warn('batch differs from the captured one (keys / shapes / non-tensor values)%s: this step runs eagerly'
