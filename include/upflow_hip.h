@@ -733,6 +733,22 @@ int upf_frames_u8_assemble(const unsigned char* src1, const unsigned char* src2,
                            float* crop1, float* crop2, float* start, int B, int H, int W, int ph, int pw,
                            double mean0, double mean1, double mean2, double stddev, void* stream);
 
+/* The 16-bit inference ingest: both frame sets, normalised as above and rounded to nearest-even to fp16 / bf16 — the bits of
+ * upf_frames_u8_assemble's raw frames followed by ATen's cast — stacked along the batch in ONE launch:
+ *   x[n,c,y,x]     = (x_dtype)raw1[n,c,y,x]   for n < B,        x[n+B,c,y,x] = (x_dtype)raw2[n,c,y,x]
+ *   xd, if not NULL: the same values in xd_dtype (the decoder's type where it differs from the pyramid's), from the same pass.
+ * src1 / src2 uint8 [B,H,W,3] contiguous, at any byte address.  x / xd [2B,3,H,W] of UPF_F16 or UPF_BF16 (chosen independently;
+ * UPF_EDTYPE otherwise), unit-stride rows, planes H * pitch elements apart, any batch stride >= 3 * H * pitch (elements).
+ * pitch == W: contiguous rows, nothing outside [.., :W] is written.  Otherwise the pitch of ops.empty_nchw — a multiple of 8 with
+ * fewer than 8 padding columns — and columns [W, pitch) of a row may receive anything; any other pitch is UPF_EINVAL.
+ * flip int32 [B] in DEVICE memory or NULL: `!= 0` mirrors that item of both frame sets.  Eight consecutive values of a channel
+ * are one 16-byte store wherever the destination is 16-byte aligned (every group of a pitched or W % 8 == 0 row of an aligned
+ * buffer).  UPF_EALIGN: x / xd not 2-byte, flip not 4-byte aligned. */
+int upf_frames_u8_stack16(const unsigned char* src1, const unsigned char* src2, const int* flip,
+                          void* x, int x_dtype, long long x_pitch, long long x_batch_stride,
+                          void* xd, int xd_dtype, long long xd_pitch, long long xd_batch_stride,
+                          int B, int H, int W, double mean0, double mean1, double mean2, double stddev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

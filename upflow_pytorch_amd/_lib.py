@@ -110,6 +110,7 @@ SIGNATURES = {
     'upf_adam_amsgrad_step': [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp],
     'upf_loss_scale_update': [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp],
     'upf_frames_u8_assemble': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp],
+    'upf_frames_u8_stack16': [_vp, _vp, _vp, _vp, _i, _ll, _ll, _vp, _i, _ll, _ll, _i, _i, _i, _d, _d, _d, _d, _vp],
 }
 
 

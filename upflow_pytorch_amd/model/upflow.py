@@ -354,8 +354,18 @@ class UPFlow_net(tools.abstract_model):
     def forward(self, input_dict: dict):
         """input_dict: im1, im2, if_loss [, im1_raw, im2_raw, start, im1_sp, im2_sp]
         -> output_dict: flow_f_out, flow_b_out, occ_fw, occ_bw [, smooth_loss, photo_loss, im1_warp,
-        im2_warp, census_loss, msd_loss]          (model/upflow.py:370-492)"""
-        im1_ori, im2_ori = input_dict['im1'], input_dict['im2']
+        im2_warp, census_loss, msd_loss]          (model/upflow.py:370-492)
+        In place of im1 / im2: frames1_u8, frames2_u8 — uint8 frames [B,H,W,3] on the GPU (the keys of Trainer.step).  Inference
+        (no_grad, if_loss False) builds the network's stacked 16-bit input from them in one launch (ops.stack_frames_u8); any
+        other setting normalises them first (ops.frames_from_u8) and runs exactly as if fed those fp32 tensors."""
+        if 'frames1_u8' in input_dict or 'frames2_u8' in input_dict:
+            if 'im1' in input_dict or 'im2' in input_dict:
+                raise ValueError('UPFlow_net.forward: pass im1 / im2 or frames1_u8 / frames2_u8, not both')
+            im1_ori, im2_ori = input_dict['frames1_u8'].contiguous(), input_dict['frames2_u8'].contiguous()
+            if torch.is_grad_enabled() or input_dict['if_loss'] or not im1_ori.is_cuda:
+                im1_ori, im2_ori = ops.frames_from_u8(im1_ori), ops.frames_from_u8(im2_ori)
+        else:
+            im1_ori, im2_ori = input_dict['im1'], input_dict['im2']
         if input_dict['if_loss'] and self.conf.input_or_sp_input != 1:
             im1, im2 = input_dict['im1_sp'], input_dict['im2_sp']
         else:
@@ -472,6 +482,16 @@ class UPFlow_net(tools.abstract_model):
             # batch halve the launch count and double every convolution's batch; `stacked_training = False` restores
             # the reference's per-direction schedule below)
             B = x1_raw.shape[0]
+            if x1_raw.dtype == torch.uint8:
+                # uint8 frames [B,H,W,3] (forward sends them here under no_grad on the GPU only): X — and the decoder's Xd, below —
+                # come from ONE launch that reads the bytes once, with the bits and the layout of the casts of the fp32 frames
+                ddt = self.flow_estimators.conv1[0].weight.dtype
+                if ddt == cdt:
+                    return self._forward_stacked(ops.stack_frames_u8(x1_raw, x2_raw, cdt, pitched=self._pitched()), B)
+                if ddt == torch.float32 or cdt == torch.float32:
+                    raise ops.UpflowHipError('pyramid_dtype: 16-bit GPU inference only')
+                X, Xd = ops.stack_frames_u8(x1_raw, x2_raw, cdt, ddt, pitched=self._pitched())
+                return self._forward_stacked(X, B, frames_dec=Xd)
             # (16-bit inference: rows pitched to 16 bytes when the frame width is ragged — KITTI's native 1242 — so that the stem
             # and the first pyramid stage take the aligned kernels; ops.empty_nchw.  `_no_pitch = True`: contiguous everywhere)
             X = ops.empty_nchw((2 * B,) + tuple(x1_raw.shape[1:]), cdt, x1_raw.device,
@@ -671,7 +691,12 @@ class UPFlow_net(tools.abstract_model):
                 ops.corr81_norm_forward_raw(pair[0], pair[1], out=slot[:, :nc], leaky_slope=0.1)
             else:
                 normed = ops.normalize(pair.reshape(2 * nb, C, H, W))         # rows are (item, channel): one launch pair
-                ops.corr81_forward_raw(normed[:nb], normed[nb:], out=slot[:, :nc], leaky_slope=0.1)
+                if normed.dtype == slot.dtype:
+                    ops.corr81_forward_raw(normed[:nb], normed[nb:], out=slot[:, :nc], leaky_slope=0.1)
+                else:
+                    # (`pyramid_dtype` at a level the fused launch does not take — fewer than 4 rows, e.g. 64x512 frames' 1x8: the
+                    # plain cost volume writes its features' type, so its result is cast into the decoder's slot; this raised before)
+                    slot[:, :nc].copy_(ops.corr81_forward_raw(normed[:nb], normed[nb:], leaky_slope=0.1))
             if f16 is None:
                 ops.flow_update(flow_up, out=slot[:, nc + 32:])
             _, res = est.forward_in_buffer(buf)

@@ -2613,3 +2613,56 @@ def assemble_train_batch(frames1_u8, frames2_u8, aug, crop_size, normalize=True)
     aug = aug.to(device=frames1_u8.device, dtype=torch.int32, non_blocking=True).contiguous()
     raw1, raw2, crop1, crop2, start = _frames_u8_assemble('assemble_train_batch', frames1_u8, frames2_u8, aug, ph, pw, normalize, True)
     return {'im1': crop1, 'im2': crop2, 'im1_raw': raw1, 'im2_raw': raw2, 'start': start}
+
+
+def _flip_or_raise(name, flip, B):
+    if flip is not None and (not torch.is_tensor(flip) or flip.dtype != torch.int32 or tuple(flip.shape) != (B,)):
+        raise UpflowHipError('%s: flip must be an int32 tensor [%d], got %s' % (name, B, (tuple(flip.shape), flip.dtype) if torch.is_tensor(flip) else type(flip)))
+    return flip
+
+
+def stack_frames_u8(frames1_u8, frames2_u8, dtype, dec_dtype=None, pitched=True, normalize=True, flip=None, out=None, out_dec=None):
+    """The network's stacked input straight from uint8 frames [B,H,W,3]: X [2B,3,H,W] of `dtype`, items n < B = frames1_u8[n],
+    items n + B = frames2_u8[n] (UPFlow_net._forward_stacked), every value the bits of frames_from_u8(...).to(dtype) — in ONE
+    launch that reads each source byte once (upf_frames_u8_stack16).  dec_dtype (the decoder's type where to_inference gave it
+    another 16-bit type than the pyramid's): a second tensor Xd of that type from the same launch -> (X, Xd); None or `dtype`:
+    X alone.  Outputs are ops.empty_nchw(pitched=pitched) tensors unless `out` / `out_dec` are given ([2B,3,H,W] of the type,
+    contiguous rows or rows padded as ops.empty_nchw pads them).  flip: optional int32 device tensor [B], != 0 mirrors that item
+    of both frame sets.  dtype = torch.float32 (the parity mode): upf_frames_u8_assemble writes the two halves of a contiguous X."""
+    who = 'stack_frames_u8'
+    _u8_frames(who, frames1_u8)
+    _u8_frames(who, frames2_u8, like=frames1_u8)
+    B, H, W, _ = frames1_u8.shape
+    dev = _lib.check_gpu(frames1_u8, frames2_u8, _flip_or_raise(who, flip, B))
+    if dtype not in _lib._DTYPES or (dec_dtype is not None and dec_dtype not in _lib._DTYPES):
+        raise UpflowHipError('%s: float32 / float16 / bfloat16 outputs only, got %s / %s' % (who, dtype, dec_dtype))
+    dual = dec_dtype is not None and dec_dtype != dtype
+    if dual and torch.float32 in (dtype, dec_dtype):
+        raise UpflowHipError('%s: a second output type is for two 16-bit types (got %s and %s)' % (who, dtype, dec_dtype))
+    if out_dec is not None and not dual:
+        raise UpflowHipError('%s: out_dec given without a dec_dtype that differs from dtype' % who)
+    shape = (2 * B, 3, H, W)
+    outs = []
+    for name, t, dt in (('out', out, dtype), ('out_dec', out_dec, dec_dtype))[:2 if dual else 1]:
+        if t is None:
+            t = empty_nchw(shape, dt, dev, pitched=pitched)
+        elif not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
+            raise UpflowHipError('%s: `%s` must be a %s tensor %s on %s' % (who, name, dt, shape, dev))
+        outs.append((t, _out_pitch_or_raise(t, '%s: `%s`' % (who, name))))
+    consts = _ingest_constants(normalize)
+    X, px = outs[0]
+    if dtype == torch.float32:
+        if not X.is_contiguous():
+            raise UpflowHipError('%s: a float32 `out` must be contiguous' % who)
+        aug = None
+        if flip is not None:
+            aug = torch.zeros((B, 3), dtype=torch.int32, device=dev)
+            aug[:, 2] = flip
+        _lib.launch(dev, 'upf_frames_u8_assemble', _lib.ptr(frames1_u8), _lib.ptr(frames2_u8), _lib.ptr(aug), _lib.ptr(X[:B]), _lib.ptr(X[B:]),
+                    None, None, None, B, H, W, 0, 0, *consts)
+        return X
+    Xd, pd = outs[1] if dual else (None, 0)
+    _lib.launch(dev, 'upf_frames_u8_stack16', _lib.ptr(frames1_u8), _lib.ptr(frames2_u8), _lib.ptr(flip),
+                _lib.ptr(X), _lib.dtype_code(X), px, X.stride(0), _lib.ptr(Xd), _lib.dtype_code(Xd) if dual else 0, pd, Xd.stride(0) if dual else 0,
+                B, H, W, *consts)
+    return (X, Xd) if dual else X

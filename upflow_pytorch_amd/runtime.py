@@ -9,25 +9,39 @@ only enqueue work on the given stream, which is what makes them capturable.
 import torch
 
 
+def frames_bhw(im):
+    """(B, H, W) of a frame batch: [B,3,H,W], or uint8 frames [B,H,W,3] as they were decoded."""
+    if im.dtype == torch.uint8:
+        B, H, W, _ = im.shape
+    else:
+        B, _, H, W = im.shape
+    return B, H, W
+
+
 class GraphedInference:
     """net(input_dict) for a fixed (B,H,W): static input buffers, captured forward, static outputs.
 
         runner = GraphedInference(net, B, H, W)
         out = runner(im1, im2)          # dict of tensors owned by the runner (valid until next call)
-    """
+
+    in_dtype=torch.uint8: the static inputs are uint8 frames [B,H,W,3] and the captured forward begins with the launch that
+    normalises, transposes, casts and stacks them (ops.stack_frames_u8) — a quarter of the fp32 frames' bytes per load."""
 
     def __init__(self, net, B, H, W, in_dtype=torch.float32, device=None, warmup=3, check_weights=True):
         self.net = net
         self.check_weights = check_weights
         p = next(net.parameters())
         self.device = device if device is not None else p.device
-        self.im1 = torch.zeros(B, 3, H, W, dtype=in_dtype, device=self.device)
+        self.u8 = in_dtype == torch.uint8
+        self.im1 = torch.zeros((B, H, W, 3) if self.u8 else (B, 3, H, W), dtype=in_dtype, device=self.device)
         self.im2 = torch.zeros_like(self.im1)
         self.graph = None
         self.out = None
         self._capture(warmup)
 
     def _forward(self):
+        if self.u8:
+            return self.net({'frames1_u8': self.im1, 'frames2_u8': self.im2, 'if_loss': False})
         return self.net({'im1': self.im1, 'im2': self.im2, 'if_loss': False})
 
     def _capture(self, warmup):
@@ -215,7 +229,7 @@ class ShapeCachedInference:
         if r is None:
             if len(self._runners) >= self.max_shapes:
                 self._runners.popitem(last=False)
-            B, _, H, W = im1.shape
+            B, H, W = frames_bhw(im1)
             r = GraphedInference(self.net, B, H, W, in_dtype=im1.dtype, device=im1.device, warmup=self.warmup)
             self._runners[key] = r
             self.captures += 1
@@ -265,7 +279,7 @@ class PipelinedEvaluation:
             self.synchronize()                 # (captures use the legacy stream semantics of the warm-up: nothing else in flight)
             if len(self._pools) >= self.max_shapes:
                 self._pools.popitem(last=False)
-            B, _, H, W = im1.shape
+            B, H, W = frames_bhw(im1)
             pool = [GraphedInference(self.net, B, H, W, in_dtype=im1.dtype, device=self.device, warmup=self.warmup if i == 0 else 1)
                     for i in range(self.n)]
             self._pools[key] = pool

@@ -48,14 +48,9 @@ class Test_model(tools.abs_test_model):
             if streams > 1:
                 self.pipe = PipelinedEvaluation(net, streams=streams)
 
-    @staticmethod
-    def _fp32_frames(im):
-        """uint8 frames [B,H,W,3] (kitti_flow.kitti_train(name, u8=True)) -> the fp32 [B,3,H,W] tensor the host data path builds
-        from them, bit for bit, in one launch (ops.frames_from_u8); anything else is returned as it came."""
-        if torch.is_tensor(im) and im.dtype == torch.uint8:
-            from . import ops
-            return ops.frames_from_u8(im.contiguous())
-        return im
+    # uint8 frames [B,H,W,3] (kitti_flow.kitti_train(name, u8=True)) go to the runner, or to the network, as they came: the runner
+    # keeps uint8 static inputs, and the network's first launch builds its stacked input from them — the bits of the host data
+    # path's fp32 tensors cast to the network's type (ops.stack_frames_u8), inside the captured graph
 
     def eval_forward_stream(self, pairs):
         """pairs: iterable of (im1, im2) -> generator of flow_fw, in order, with several pairs in flight; every yielded tensor is the
@@ -65,7 +60,7 @@ class Test_model(tools.abs_test_model):
                 yield self.eval_forward(im1, im2, 0)
             return
         with torch.no_grad():
-            for out in self.pipe.map((self._fp32_frames(im1), self._fp32_frames(im2)) for im1, im2 in pairs):
+            for out in self.pipe.map(pairs):
                 # (a copy, like eval_forward's: the slot's output is overwritten when the generator advances, and eval_save_result
                 # — a hook whose documented purpose is to store / save predflows — may keep it; 3.7 MB per KITTI pair.  ADVICE r5)
                 yield out['flow_f_out'].clone()
@@ -73,11 +68,11 @@ class Test_model(tools.abs_test_model):
     def eval_forward(self, im1, im2, gt, *args):
         # === network output                                 (test.py:40-47)
         with torch.no_grad():
-            im1, im2 = self._fp32_frames(im1), self._fp32_frames(im2)
             if self.runner is not None:
                 output_dict = self.runner(im1, im2)
                 return output_dict['flow_f_out'].clone()      # (the runner owns its outputs: the caller keeps predflow across calls)
-            output_dict = self.net_work({'im1': im1, 'im2': im2, 'if_loss': False})
+            keys = ('frames1_u8', 'frames2_u8') if torch.is_tensor(im1) and im1.dtype == torch.uint8 else ('im1', 'im2')
+            output_dict = self.net_work({keys[0]: im1, keys[1]: im2, 'if_loss': False})
             return output_dict['flow_f_out']
 
     def eval_save_result(self, save_name, predflow, *args, **kwargs):
