@@ -343,7 +343,8 @@ def warp(x, flow, mask_mode='literal'):
     xf = x.reshape(B, C, H * W)
     out = None
     for w, (px, py), m in zip(wts, pos, inb):
-        idx = (py.clamp(0, H - 1) * W + px.clamp(0, W - 1)).long().view(B, 1, H * W).expand(B, C, H * W)
+        # (a NaN position has no index: its taps are out of bounds and get weight 0 below, whichever pixel is gathered)
+        idx = torch.nan_to_num(py.clamp(0, H - 1) * W + px.clamp(0, W - 1), nan=0.0).long().view(B, 1, H * W).expand(B, C, H * W)
         v = torch.gather(xf, 2, idx).view(B, C, H, W)
         term = v * torch.where(m, w, torch.zeros_like(w)).unsqueeze(1)
         out = term if out is None else out + term
@@ -448,7 +449,9 @@ def occ_check(flow_f, flow_b, alpha1=0.1, alpha2=0.5):
         xx = torch.arange(W, dtype=torch.float32).view(1, 1, 1, W)
         yy = torch.arange(H, dtype=torch.float32).view(1, 1, H, 1)
         px, py = xx + flow[:, 0:1], yy + flow[:, 1:2]
-        return ((px <= W - 1) & (px >= 0) & (py <= H - 1) & (py >= 0)).float()
+        # utils/tools.py:663-667: ones, zeroed where px > W-1, px < 0, py > H-1, py < 0 — a NaN position fails all four comparisons
+        # and stays IN the frame (`(px <= W-1) & ...` would mark it outgoing)
+        return (~((px > W - 1) | (px < 0) | (py > H - 1) | (py < 0))).float()
 
     def merge(occ, out):
         return ((occ == 1) | (out == 0)).float()

@@ -3,7 +3,8 @@ conv_wgrad.hip), their fp64 reference, the guard that makes bit equality a fair 
 Shared by tests/test_hip_conv_exact.py (GPU) and tests/test_exact_model_cpu.py (the conditions, no GPU).  Plain torch, no GPU import.
 The cost-volume section does the same for csrc/corr81_*.hip (tests/test_hip_corr_exact.py); the last section models the sampling
 kernels — backward warp and flow resize — whose weights come out of an fp32 position chain (tests/test_hip_warp_exact.py,
-tests/test_hip_resize_exact.py).
+tests/test_hip_resize_exact.py); the sections after it model the feature normalisation (tests/test_hip_norm_exact.py), the occlusion
+check, the soft census distance and the SGU interpolation-blend (tests/test_hip_blend_exact.py).
 
 The idea: every operand sits on a grid (an integer multiple of a power of two, few significant bits).  Every product is then a
 multiple of the QUANTUM (the product of the two grid steps) and so is every partial sum, in any order.  If the sum of the ABSOLUTE
@@ -1262,3 +1263,530 @@ def upsample_bwd_route(h, w, H, W, BC=2):
         return 'wg' + ('_notable' if ni > 160 or nj > 160 else '')
     name = 'group16' if fp > 200 else ('group4' if fp > 16 else 'group1')
     return name + ('_notable' if nj > 24 else '')
+
+
+# ---- feature normalisation (csrc/misc.hip normalize_*; tests/test_hip_norm_exact.py) ---------------------------------------------------
+# General regime only: the statistics are long fp32 sums.  The reference is fp64 from the STORED operand (mean, unbiased variance,
+# std = sqrt(var + float32(1e-16))); the bounds count fp32 roundings along the longest path of the route the host code selects, which
+# `normalize_route` reads off normalize_nseg / stats_wave_form / the `vec` condition of csrc/misc.hip.
+NORM_EPS = float(np.float32(1e-16))
+NORM_NT, NORM_WAVE = 512, 64
+NORM_SPIKE = 512.0
+# name -> (B, C, H, W), elements past a 16-byte boundary, spike rows
+NORM_CASES = {'hw2': ((1, 3, 1, 2), 0, False), 'hw63_9rows': ((3, 3, 7, 9), 0, False), 'hw64': ((1, 2, 8, 8), 0, False),
+              'hw64_misaligned': ((1, 2, 8, 8), 1, False), 'wave_limit': ((2, 256, 64, 64), 0, False), 'block_4104': ((2, 256, 57, 72), 0, False), 'block_4104_misaligned': ((2, 256, 57, 72), 1, False),
+              'seg2_2048': ((1, 1, 64, 64), 0, False), 'seg2_2052': ((1, 1, 57, 72), 0, False), 'seg2_2050': ((1, 1, 50, 82), 0, False), 'seg2_ragged': ((1, 2, 61, 69), 0, False),
+              'seg4_ragged': ((1, 3, 91, 91), 0, False),
+              'spike_wave': ((2, 256, 64, 64), 0, True), 'spike_block': ((1, 2, 112, 256), 0, True)}
+NORM_WAVE_ONLY = ('wave_limit', 'block_4104_misaligned', 'spike_wave', 'spike_block')          # no fp32 run: the 2.1 M-element cases and the 16-bit pivot's spike rows
+NORM_BWD_HW = (2, 63, 513, 4104)
+NORM_BWD_ROWS = 3
+
+
+def normalize_route(N, HW, dtype, aligned=True):
+    """normalize_nseg, stats_wave_form and the `vec` condition of upf_normalize_forward -> (form 'wave' / 'block', nseg, seglen, vec)."""
+    nseg = 1
+    while N * nseg < 512 and HW // (nseg * 2) >= 2048:
+        nseg *= 2
+    seglen = (HW + nseg - 1) // nseg
+    vn = 4 if dtype == F32 else 8
+    vec = HW % vn == 0 and seglen % vn == 0 and bool(aligned)
+    form = 'wave' if nseg == 1 and HW <= 4096 and dtype != F32 else 'block'
+    return form, nseg, seglen, vec
+
+
+def norm_roundings(route, dtype):
+    """k of gamma_k: the per-lane sum (V elements per trip, ceil(seglen / (threads * V)) trips), 9 for the widest reduction tree,
+    8 for the operations of each norm_merge_add."""
+    form, nseg, seglen, vec = route
+    V = (4 if dtype == F32 else 8) if vec else 1
+    threads = NORM_WAVE if form == 'wave' else NORM_NT
+    return V * (-(-seglen // (threads * V))) + 9 + 8 * (nseg - 1)
+
+
+def norm_forward_ref(x, route, dtype):
+    """x [N, HW] (values stored in `dtype`).  -> dict mean, std, rstd, y (fp64), kappa, b_mean (absolute), b_rstd (relative), b_y
+    (absolute) per the bounds of DESIGN.md 4.12; the pivot K of a segment is its first element (16-bit), 0 for fp32's two sweeps."""
+    x = np.asarray(x, dtype=np.float64)
+    N, HW = x.shape
+    form, nseg, seglen, vec = route
+    mean = x.mean(1)
+    m2 = ((x - mean[:, None]) ** 2).sum(1)
+    std = np.sqrt(m2 / (HW - 1) + NORM_EPS)
+    gk = gamma(norm_roundings(route, dtype))
+    absdev, pivot2 = np.zeros(N), np.zeros(N)
+    for s in range(nseg):
+        seg = x[:, s * seglen:min(HW, (s + 1) * seglen)]
+        K = seg[:, :1] if dtype != F32 else np.zeros((N, 1))
+        absdev += np.abs(seg - K).sum(1)
+        pivot2 += seg.shape[1] * (seg.mean(1) - K[:, 0]) ** 2
+    kappa = 1.0 + pivot2 / np.maximum(m2, 1e-300)
+    b_mean = gk * absdev / HW + U32 * np.abs(mean)
+    b_rstd = gk * (kappa if dtype != F32 else np.ones(N)) + 3 * U32
+    y = (x - mean[:, None]) / std[:, None]
+    b_y = np.abs(y) * (b_rstd + 2 * U32)[:, None] + (b_mean / std)[:, None]
+    return dict(mean=mean, std=std, rstd=1.0 / std, y=y, kappa=kappa, b_mean=b_mean, b_rstd=b_rstd, b_y=b_y)
+
+
+def _to_dtype(a, dtype):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dtype).float().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def norm_case(name, dtype):
+    """-> dict x [N, HW] (np.float32 stored in `dtype`), shape, misalign, spike; rows of N(m, s) with m in [-2, 2] and s in [1/4, 2]
+    per row — a spike case: N(0.5, 2^-4) with the row's first element 0.5 + 512 (rounded to the type).  Shared, never written to."""
+    shape, misalign, spike = NORM_CASES[name]
+    B, C, H, W = shape
+    N, HW = B * C, H * W
+    rng = np.random.RandomState(seed_of('norm', name, SAMP_NAMES[dtype]))
+    if spike:
+        x = 0.5 + 2.0 ** -4 * rng.standard_normal((N, HW))
+        x[:, 0] = 0.5 + NORM_SPIKE
+    else:
+        dev = rng.choice([-1.0, 1.0], (N, HW)) * rng.uniform(0.75, 1.75, (N, HW))
+        x = rng.uniform(-2, 2, (N, 1)) + 2.0 ** rng.uniform(-2, 1, (N, 1)) * dev
+    return dict(x=_to_dtype(x, dtype), shape=shape, N=N, HW=HW, misalign=misalign, spike=spike, name=name)
+
+
+def norm_dtypes(name):
+    return SAMP_DTYPES[:2] if name in NORM_WAVE_ONLY else SAMP_DTYPES
+
+
+def norm_backward_ref(y, gy, rstd):
+    """gx = r * (g - mean(g) - y * sum(g y) / (HW - 1)) in fp64 -> (gx, bound): gamma_k on sum |g| / HW + |y| sum |g y| / (HW - 1) + |g|,
+    times |r|, k = ceil(HW / 512) + 9 + 4."""
+    y, g, r = (np.asarray(a, dtype=np.float64) for a in (y, gy, rstd))
+    N, HW = y.shape
+    gx = r[:, None] * (g - g.mean(1, keepdims=True) - y * (g * y).sum(1, keepdims=True) / (HW - 1))
+    k = -(-HW // NORM_NT) + 9 + 4
+    mag = np.abs(g).sum(1, keepdims=True) / HW + np.abs(y) * np.abs(g * y).sum(1, keepdims=True) / (HW - 1) + np.abs(g)
+    return gx, gamma(k) * mag * np.abs(r)[:, None]
+
+
+@functools.lru_cache(maxsize=None)
+def norm_bwd_case(HW, dtype):
+    """-> y, gy [NORM_BWD_ROWS, HW] (np.float32 stored in `dtype`), rstd [rows] np.float32."""
+    rng = np.random.RandomState(seed_of('normbwd', HW, SAMP_NAMES[dtype]))
+    y, gy = (_to_dtype(rng.standard_normal((NORM_BWD_ROWS, HW)), dtype) for _ in range(2))
+    return y, gy, (2.0 ** rng.uniform(-2, 2, NORM_BWD_ROWS)).astype(np.float32)
+
+
+# ---- occlusion check (csrc/misc.hip occ_check_kernel; tests/test_hip_blend_exact.py) ---------------------------------------------------
+OCC_ALPHA = (0.1, 0.5)
+OCC_DYADIC = [(2, 5, 9), (2, 9, 17), (2, 17, 65)]
+OCC_GENERAL = [(2, 7, 13), (2, 6, 70), (1, 1, 5), (1, 5, 1)]
+
+
+def occ_ref(ff, fb, a1, a2):
+    """occ_check_kernel step by step: one np.float32 operation per step (the magnitude with its association, thr = fl(fl(a1 mag) + a2),
+    the comparisons, the four negated frame comparisons); only the four-tap sums are taken in fp64 (exact in the dyadic regime).
+    -> (occ_fw, occ_bw [B,H,W] np.float32 of 0 / 1, undecided_fw, undecided_bw bool: |lhs - thr| <= gamma_6 sum |terms| + 2 u thr, where
+    the fp32 association of the tap sum may decide the comparison either way)."""
+    ff, fb = (np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (ff, fb))
+    B, _, H, W = ff.shape
+    a1, a2 = np.float32(a1), np.float32(a2)
+    with np.errstate(all='ignore'):
+        mag = (np.abs(ff[:, 0]) + np.abs(ff[:, 1])) + (np.abs(fb[:, 0]) + np.abs(fb[:, 1]))
+        thr = a1 * mag + a2
+        assert mag.dtype == np.float32 and thr.dtype == np.float32
+        out = []
+        for own, other in ((ff, fb), (fb, ff)):
+            t = taps32(own, H, W)
+            w64, wa = warp_forward_ref(other, t, 'none')
+            w32 = w64.astype(np.float32)
+            lhs = np.abs(own[:, 0] + w32[:, 0]) + np.abs(own[:, 1] + w32[:, 1])
+            assert lhs.dtype == np.float32
+            consistent = lhs < thr
+            px, py = t['px'], t['py']
+            inside = ~(px > np.float32(W - 1)) & ~(px < np.float32(0)) & ~(py > np.float32(H - 1)) & ~(py < np.float32(0))
+            lhs64 = np.abs(own[:, 0].astype(np.float64) + w64[:, 0]) + np.abs(own[:, 1].astype(np.float64) + w64[:, 1])
+            terms = np.abs(own[:, 0]).astype(np.float64) + np.abs(own[:, 1]) + wa[:, 0] + wa[:, 1]
+            thr64 = thr.astype(np.float64)
+            # (an infinite or NaN left-hand side is decided: the fp32 sum is infinite or NaN in any association — one source, one sign)
+            undecided = np.isfinite(lhs64) & np.isfinite(thr64) & (np.abs(lhs64 - thr64) <= gamma(6) * np.where(np.isfinite(terms), terms, 0.0) + 2 * U32 * thr64)
+            out.append(((consistent | ~inside).astype(np.float32), undecided, consistent, inside))
+    return out[0], out[1]
+
+
+@functools.lru_cache(maxsize=None)
+def occ_case(shape, dyadic):
+    """-> dict ff, fb [B,2,H,W] np.float32 and the counts the case claims.  fb is minus ff sampled at the target plus noise of two
+    sizes (0.05: consistent, 2: not); the top rows point out of the frame; column 0 holds positions exactly on the frame (px == W-1,
+    == 0, fx == -0.0) and — general regime — the first fp32 value beyond each, the same for py in row 0; the general regime ends with
+    a NaN, a +inf and a -1e30 flow."""
+    B, H, W = shape
+    rng = np.random.RandomState(seed_of('occ', shape, dyadic))
+    q = (lambda v: np.round(v / FLOW_STEP) * FLOW_STEP) if dyadic else (lambda v: v)
+    ff = q(np.clip(rng.uniform(-1.5, 1.5, (B, 2, 1, 1)) + 0.4 * rng.standard_normal((B, 2, H, W)), -4, 4)).astype(np.float32)
+    back = warp_forward_ref(ff, taps32(-ff, H, W), 'none')[0]
+    noise = np.where(rng.rand(B, 1, H, W) < 0.5, 0.05, 2.0) * rng.standard_normal((B, 2, H, W))
+    fb = q(np.clip(-back + noise, -6, 6)).astype(np.float32)
+    if H > 2:
+        ff[:, 1, 0] = q(-1.0 - rng.uniform(0, 2, (B, W))).astype(np.float32)             # a band that leaves the frame at the top
+        fb[:, 0, H - 1] = q(W + rng.uniform(0, 2, (B, W))).astype(np.float32)            # ... and on the right
+    edge = 0
+    one = np.float32(1)
+    xs = [np.float32(W - 1), np.float32(0), np.float32(-0.0)]
+    ys = [np.float32(H - 1), np.float32(0), np.float32(-0.0)]
+    if not dyadic:
+        xs += [np.nextafter(np.float32(W - 1), np.float32(np.inf)), np.nextafter(np.float32(0), -one)]
+        ys += [np.nextafter(np.float32(H - 1), np.float32(np.inf)), np.nextafter(np.float32(0), -one)]
+    for f in (ff, fb):
+        for k, v in enumerate(xs):                                                      # column 0: px = 0 + fx
+            if H > 1:
+                f[:, 0, 1 + k % (H - 1), 0] = v
+                edge += B
+        for k, v in enumerate(ys):                                                      # row 0: py = 0 + fy
+            if W > 1:
+                f[:, 1, 0, 1 + k % (W - 1)] = v
+                edge += B
+    nonfinite = 0
+    if not dyadic and H * W >= 3:
+        for (n, c, i, j), v in zip(nonfinite_places(B, H, W), NONFINITE):
+            (ff if n == 0 else fb)[n, c, i, j] = v
+            nonfinite += 1
+    if dyadic:
+        fin = np.concatenate([ff.ravel(), fb.ravel()]).astype(np.float64)
+        assert np.all(fin / FLOW_STEP == np.round(fin / FLOW_STEP)) and np.all(np.abs(fin) <= 70)
+        assert is_dyadic_size(H) and is_dyadic_size(W)
+    return dict(ff=ff, fb=fb, shape=shape, dyadic=dyadic, edge=edge, nonfinite=nonfinite)
+
+
+def occ_counts(c, ref):
+    """consistent / in, inconsistent / in, outgoing pixels (both directions together), from the model alone."""
+    cons = np.concatenate([ref[0][2].ravel(), ref[1][2].ravel()])
+    ins = np.concatenate([ref[0][3].ravel(), ref[1][3].ravel()])
+    return dict(consistent_in=int((cons & ins).sum()), inconsistent_in=int((~cons & ins).sum()), outgoing=int((~ins).sum()),
+                edge=c['edge'], nonfinite=c['nonfinite'])
+
+
+# ---- soft census distance (csrc/misc.hip census_*_kernel; tests/test_hip_blend_exact.py) ------------------------------------------------
+# General regime only: the kernels use the hardware reciprocal and reciprocal square root (1 ulp = 2 u each).
+CENSUS_A, CENSUS_B = float(np.float32(0.81)), float(np.float32(0.1))
+CENSUS_SIZES = [(2, 3), (7, 9), (17, 65)]
+CENSUS_R = (1, 3, 8)
+CENSUS_KINDS = ('random', 'equal', 'constant')
+
+
+@functools.lru_cache(maxsize=None)
+def census_case(size, kind):
+    """-> g1, g2 (grey images in [0, 1]), G (grad of dist): [2, H, W] np.float32.  'equal': g2 is g1; 'constant': g1 is 0.375 everywhere."""
+    H, W = size
+    rng = np.random.RandomState(seed_of('census', size, kind))
+    g1, g2 = (rng.uniform(0, 1, (2, H, W)).astype(np.float32) for _ in range(2))
+    if kind == 'equal':
+        g2 = g1.copy()
+    if kind == 'constant':
+        g1 = np.full((2, H, W), 0.375, dtype=np.float32)
+    return g1, g2, rng.standard_normal((2, H, W)).astype(np.float32)
+
+
+def _census_terms(u1, u2):
+    """One neighbour's term and its derivatives in fp64 with a running first-order error bound of the kernel's fp32 evaluation (u per
+    IEEE operation, 2 u per rsq / rcp), doubled for the second-order terms.  -> term, e_term, c1, e_c1, c2, e_c2 (u1, u2: the fp64
+    differences of the stored values; their own rounding is the first entry of the chain)."""
+    u = U32
+    e1, e2 = u * np.abs(u1), u * np.abs(u2)
+    q1, q2 = CENSUS_A + u1 * u1, CENSUS_A + u2 * u2
+    eq1, eq2 = 2 * np.abs(u1) * e1 + u * u1 * u1 + u * q1, 2 * np.abs(u2) * e2 + u * u2 * u2 + u * q2
+    r1, r2 = q1 ** -0.5, q2 ** -0.5
+    p1, p2 = 0.5 * eq1 / q1 + 2 * u, 0.5 * eq2 / q2 + 2 * u                           # relative errors of r1, r2
+    t1, t2 = u1 * r1, u2 * r2
+    et1, et2 = e1 * r1 + np.abs(t1) * (p1 + u), e2 * r2 + np.abs(t2) * (p2 + u)
+    df = t1 - t2
+    edf = et1 + et2 + u * np.abs(df)
+    d = df * df
+    ed = 2 * np.abs(df) * edf + u * d
+    s = CENSUS_B + d
+    es = ed + u * s
+    inv = 1.0 / s
+    pinv = es / s + 2 * u
+    term = d * inv
+    eterm = ed * inv + term * (pinv + u)
+    kf = CENSUS_B * inv * inv * 2.0 * df * CENSUS_A
+    ekf = np.abs(kf) * (2 * pinv + 4 * u) + CENSUS_B * inv * inv * 2.0 * CENSUS_A * edf
+    c1, c2 = kf * r1 ** 3, -kf * r2 ** 3
+    ec1, ec2 = ekf * r1 ** 3 + np.abs(c1) * 3 * (p1 + u), ekf * r2 ** 3 + np.abs(c2) * 3 * (p2 + u)
+    return term, 2 * eterm, c1, 2 * ec1, c2, 2 * ec2
+
+
+def census_ref(g1, g2, G, R):
+    """fp64 from the stored grey images, zero padding, the constants float32(0.81) and float32(0.1).  -> dict dist, b_dist, gg1, gg2
+    (the adjoint from BOTH roles of a pixel: centre of its own terms, neighbour of offset k of every centre inside the image),
+    b_gg1, b_gg2 (the kernel's terms gsum * c_k with their running bounds, plus gamma_K of the accumulation, K = (2R+1)^2)."""
+    a, b, G = (np.asarray(v, dtype=np.float64) for v in (g1, g2, G))
+    B, H, W = a.shape
+    K = (2 * R + 1) ** 2
+    pa, pb, pG = (np.pad(v, ((0, 0), (R, R), (R, R))) for v in (a, b, G))
+    inside = np.pad(np.ones((B, H, W), dtype=bool), ((0, 0), (R, R), (R, R)))
+    dist, e_dist, a_dist = np.zeros_like(a), np.zeros_like(a), np.zeros_like(a)
+    gg = [np.zeros_like(pa), np.zeros_like(pa)]
+    e_gg, a_gg = [np.zeros_like(a), np.zeros_like(a)], [np.zeros_like(a), np.zeros_like(a)]
+    for dy in range(2 * R + 1):
+        for dx in range(2 * R + 1):
+            va, vb = pa[:, dy:dy + H, dx:dx + W], pb[:, dy:dy + H, dx:dx + W]
+            term, et, c1, ec1, c2, ec2 = _census_terms(va - a, vb - b)
+            dist += term
+            e_dist += et
+            a_dist += np.abs(term)
+            gsum = G + pG[:, dy:dy + H, dx:dx + W]                                    # the kernel's halved form: for the bound only
+            for n, (c, ec) in enumerate(((c1, ec1), (c2, ec2))):
+                gg[n][:, R:R + H, R:R + W] -= G * c                                   # centre role: du / dI(p) = -1
+                gg[n][:, dy:dy + H, dx:dx + W] += np.where(inside[:, dy:dy + H, dx:dx + W], G * c, 0.0)      # neighbour role
+                e_gg[n] += np.abs(gsum) * ec + 2 * U32 * np.abs(gsum * c)
+                a_gg[n] += np.abs(gsum * c)
+    out = dict(dist=dist, b_dist=e_dist + gamma(K) * a_dist)
+    for n in (0, 1):
+        out['gg%d' % (n + 1)] = gg[n][:, R:R + H, R:R + W]
+        out['b_gg%d' % (n + 1)] = e_gg[n] + gamma(K) * a_gg[n]
+    return out
+
+
+# ---- SGU interpolation-blend (csrc/sgu_blend.hip blend_fwd_kernel / blend_bwd_kernel; tests/test_hip_blend_exact.py) --------------------
+# flow_up = warp(flow_init; inter_flow) * (1 - m) + flow_init * m, m = sigmoid(logit), the warp without a mask.  Dyadic regime: sizes
+# with Hf-1, Wf-1 powers of two, flow_init and inter_flow on the 1/8 grid, grad_out on the fp16 gy grid, logits in {0, +100, -100}: expf
+# then returns exactly 1, a value below one ulp of 1, or inf, so m is exactly 0.5, 1 or 0 whatever the device library's expf does.
+BLEND_DTYPES = (F32, torch.bfloat16, torch.float16)
+BLEND_DYADIC = [(2, 5, 9), (2, 9, 17), (2, 17, 65), (2, 3, 129), (2, 2, 2)]
+BLEND_GENERAL = [(2, 7, 13), (2, 6, 70), (2, 1, 5), (2, 5, 1), (2, 9, 29)]
+BLEND_FINAL = [((3, 5), (9, 17)), ((4, 13), (7, 29)), ((2, 3), (17, 65))]
+BLEND_FLOW16 = [(2, 5, 9), (2, 17, 65)]
+BLEND_LOGITS = (0.0, 100.0, -100.0)
+BLEND_THREADS = 256
+BLEND_GX_TERMS = 12 * 2 + 4
+SIGMOID_ULPS = 5                                       # relative, in u: 3 ulp of expf (the OpenCL full-profile limit) + the add + the division
+
+
+def sigmoid64(v):
+    with np.errstate(all='ignore'):
+        return 1.0 / (1.0 + np.exp(-np.asarray(v, dtype=np.float64)))
+
+
+def sigmoid_of_exact_logits(v):
+    """The fp32 sigmoid of logits in {0, +100, -100}: 1 / (1 + expf(-v)) is exactly 0.5, 1 (expf below one ulp of 1) or 0 (1 / inf)."""
+    v = np.asarray(v)
+    assert np.all(np.isin(v, BLEND_LOGITS))
+    return np.where(v == 0, 0.5, np.where(v > 0, 1.0, 0.0))
+
+
+def lerp4_32(x, H, W):
+    """ly.l0 * (lx.l0 * a + lx.l1 * b) + ly.l1 * (lx.l0 * c + lx.l1 * d), every step in np.float32 (the kernels are compiled without
+    contraction).  x [B,C,h,w] np.float32 -> [B,C,H,W] np.float32."""
+    x = np.asarray(x)
+    assert x.dtype == np.float32
+    h, w = x.shape[2:]
+    yi0, yi1, yl0, yl1 = lerp32(H, h)
+    xi0, xi1, xl0, xl1 = lerp32(W, w)
+    yl0, yl1, xl0, xl1 = yl0[:, None], yl1[:, None], xl0[None, :], xl1[None, :]
+    a, b = x[:, :, yi0][:, :, :, xi0], x[:, :, yi0][:, :, :, xi1]
+    c, d = x[:, :, yi1][:, :, :, xi0], x[:, :, yi1][:, :, :, xi1]
+    with np.errstate(all='ignore'):
+        y = yl0 * (xl0 * a + xl1 * b) + yl1 * (xl0 * c + xl1 * d)
+    assert y.dtype == np.float32
+    return y
+
+
+def blend_inter(x_out, Hf, Wf):
+    """-> (inter_flow [B,2,Hf,Wf] np.float32, m [B,Hf,Wf] fp64, m32 or None).  Decoder level: the stored values and the fp64 sigmoid.
+    Final level (logits in {0, +-100} only): lerp4_32 of the stored flow times fp32(Wf / w), fp32(Hf / h), and of the exact sigmoid
+    values 0.5 / 1 / 0 — both bit for bit (m32)."""
+    x = np.asarray(x_out, dtype=np.float32)
+    h, w = x.shape[2:]
+    if (h, w) == (Hf, Wf):
+        return x[:, :2].copy(), sigmoid64(x[:, 2]), None
+    assert np.all(np.isin(x[:, 2], BLEND_LOGITS))
+    su, sv = np.float32(Wf / w), np.float32(Hf / h)
+    fl = lerp4_32(x[:, :2], Hf, Wf) * np.array([su, sv], dtype=np.float32).reshape(1, 2, 1, 1)
+    assert fl.dtype == np.float32
+    m32 = lerp4_32(sigmoid_of_exact_logits(x[:, 2:3]).astype(np.float32), Hf, Wf)[:, 0]
+    return fl, m32.astype(np.float64), m32
+
+
+def blend_forward_ref(flow_init, t, m):
+    """-> (flow_up fp64, bound fp64): gamma_7 (sum |w v| |1 - m| + |f m|) + 5 u |f - warped| (the latter for the sigmoid)."""
+    f = np.asarray(flow_init, dtype=np.float64)
+    warped, wa = warp_forward_ref(f, t, 'none')
+    m = m[:, None]
+    with np.errstate(all='ignore'):
+        fu = warped * (1.0 - m) + f * m
+        bound = gamma(7) * (wa * np.abs(1.0 - m) + np.abs(f * m)) + SIGMOID_ULPS * U32 * np.abs(f - warped)
+    return fu, bound
+
+
+def blend_ginit_model(g, t, m32):
+    """g_flow_init bit for bit GIVEN the kernel's m (np.float32): per tap in bounds rint(fp32(fp32((1 - m) g) w_k) * 2^44), plus
+    rint(fp32(m g) * 2^44) at the pixel itself, integer sums, fp32(double(q) * 2^-44)."""
+    g32 = np.asarray(g, dtype=np.float32)
+    B, _, H, W = g32.shape
+    m32 = np.asarray(m32)
+    assert m32.dtype == np.float32 and g32.shape[1] == 2
+    om = (np.float32(1) - m32)[:, None]
+    q = np.zeros((B, 2, H * W), dtype=np.int64)
+    n = np.broadcast_to(np.arange(B)[:, None, None], t['x0'].shape)
+    with np.errstate(all='ignore'):
+        og = om * g32
+        for k in range(4):
+            on = t['inb'][k]
+            yk, xk = _tap_index(t, k, H, W)
+            prod = og * t['w'][k][:, None]
+            assert prod.dtype == np.float32
+            c = np.rint(np.where(on[:, None], prod.astype(np.float64) * FIX, 0.0)).astype(np.int64)
+            for ch in range(2):
+                np.add.at(q, (n[on], ch, (yk * W + xk)[on]), c[:, ch][on])
+        own = m32[:, None] * g32
+        assert own.dtype == np.float32
+        q += np.rint(own.astype(np.float64) * FIX).astype(np.int64).reshape(B, 2, H * W)
+    assert np.all(np.abs(q) < 2 ** 53)
+    return (q.astype(np.float64) * (1.0 / FIX)).astype(np.float32).reshape(B, 2, H, W)
+
+
+def blend_pos_factor(n):
+    """((n - 1) * 0.5) * (2 / max(n - 1, 1)) in np.float32: the derivative of the sampling position with respect to the flow."""
+    return float((np.float32(n - 1) * np.float32(0.5)) * (np.float32(2) / np.float32(max(n - 1, 1))))
+
+
+def blend_backward_ref(flow_init, g, t, m):
+    """fp64 -> (gfull [B,3,H,W]: d / d inter_flow x, y and d / d m, bound [B,3,H,W]).  d / d inter_flow = (1 - m) * factor * sum_c
+    g_c d warp_c / d pos (12 products per channel, 2 channels, the two factors, the accumulation: gamma_28 on the absolute terms);
+    d / d m = sum_c g_c (f_c - warped_c) with the same count."""
+    f, g = np.asarray(flow_init, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    B, _, H, W = f.shape
+    _, gf, gfa = warp_backward_ref(f, g, t, 'none')
+    warped, wa = warp_forward_ref(f, t, 'none')
+    om = (1.0 - m)[:, None]
+    fac = np.array([blend_pos_factor(W), blend_pos_factor(H)]).reshape(1, 2, 1, 1)
+    gm = (g * (f - warped)).sum(1, keepdims=True)
+    gma = (np.abs(g) * (np.abs(f) + wa)).sum(1, keepdims=True)
+    full = np.concatenate([gf * om * fac, gm], 1)
+    bound = gamma(BLEND_GX_TERMS) * np.concatenate([gfa * np.abs(om) * fac, gma], 1)
+    return full, bound
+
+
+def blend_counts(t, B, H, W):
+    """What a backward case exercises, counted on the model (blend_bwd_kernel: pixel p of an image is thread p % 256 of workgroup
+    p / 256, lane p % 64): merged (the right-hand tap of p joins the left-hand tap of p + 1: both in bounds, equal addresses, lane
+    < 63), refused_lane63 (the same pair across lanes 63 / 0), refused_address (both in bounds, different addresses: what the address
+    comparison is for), refused_row_end (p ends a row, its right-hand tap is in bounds, no merge), outside taps per side, colliding
+    addresses, threads past HW in the last workgroup."""
+    HW = H * W
+    inb = [t['inb'][k].reshape(B, -1) for k in range(4)]
+    o = [(lambda yx: yx[0] * W + yx[1])(_tap_index(t, k, H, W)).reshape(B, -1) for k in range(4)]
+    lane = (np.arange(HW) & 63)[:-1]
+    rowend = (np.arange(HW) % W == W - 1)[:-1]
+    c = dict(merged=0, refused_lane63=0, refused_address=0, refused_row_end=0)
+    for r, l in ((1, 0), (3, 2)):
+        both = inb[r][:, :-1] & inb[l][:, 1:]
+        same = o[r][:, :-1] == o[l][:, 1:]
+        c['merged'] += int((both & same & (lane < 63)).sum())
+        c['refused_lane63'] += int((both & same & (lane == 63)).sum())
+        c['refused_address'] += int((both & ~same & (lane < 63)).sum())
+        c['refused_row_end'] += int((inb[r][:, :-1] & rowend & ~(both & same & (lane < 63))).sum())
+    hits = np.zeros((B, HW), dtype=np.int64)
+    nn = np.broadcast_to(np.arange(B)[:, None], (B, HW))
+    for k in range(4):
+        np.add.at(hits, (nn[inb[k]], o[k][inb[k]]), 1)
+    c['collisions'] = int((hits >= 2).sum())
+    x0, y0 = t['x0'], t['y0']
+    c.update(left=int((x0 < 0).sum()), right=int((x0 + 1 > W - 1).sum()), top=int((y0 < 0).sum()), bottom=int((y0 + 1 > H - 1).sum()))
+    c['past_hw'] = (-HW) % BLEND_THREADS
+    return c
+
+
+def _blend_flows(rng, B, H, W, dyadic, scale=(1.0, 1.0)):
+    """Inter-flow channels.  Dyadic: multiples of 1/8 within +-4; general: N(0, 3) with a row of +(W + 2.3) and one of -(W + 3.1) in x,
+    a column of +(H + 2.3) and one of -(H + 3.1) in y (taps outside on every side), divided by `scale` (the final level multiplies by
+    it).  From 4 rows up the lower half but the last row holds ONE fractional displacement: neighbouring lanes then sample neighbouring pixels, which
+    is what the backward's lane merge is for (across lanes 63 / 64 and across row ends it must refuse)."""
+    if dyadic:
+        f = np.round(rng.uniform(-4, 4, (B, 2, H, W)) / FLOW_STEP) * FLOW_STEP
+        const = (0.375, -0.25)
+    else:
+        f = 3.0 * rng.standard_normal((B, 2, H, W))
+        const = (0.3, -0.7)
+    if H >= 4:
+        f[:, 0, (H + 1) // 2:H - 1], f[:, 1, (H + 1) // 2:H - 1] = const
+    if not dyadic:
+        f[:, 0, 0], f[:, 0, min(1, H - 1)] = -(W + 3.1), W + 2.3
+        f[:, 1, :, (2 * W) // 3], f[:, 1, :, W // 3] = -(H + 3.1), H + 2.3
+    return f / np.array(scale).reshape(1, 2, 1, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def blend_case(shape, dtype, regime, lo=None):
+    """-> dict flow_init [B,2,Hf,Wf], x_out [B,3,h,w] (np.float32, stored in `dtype`), g (grad of flow_up), inter (np.float32), m (fp64),
+    m32 (bit-exact m where the model has one), t (taps32 of inter).  regime 'dyadic' / 'general' / 'final' (x_out at `lo` = (h, w),
+    logits in {0, +-100}) / 'nonfinite' (general with a NaN and a +inf inter flow)."""
+    B, Hf, Wf = shape
+    h, w = lo if lo else (Hf, Wf)
+    dyadic = regime == 'dyadic'
+    rng = np.random.RandomState(seed_of('blend', shape, SAMP_NAMES[dtype], regime, lo))
+    gg = GRIDS[torch.float16]['gy']
+    if dyadic:
+        f0 = np.round(rng.uniform(-4, 4, (B, 2, Hf, Wf)) / FLOW_STEP) * FLOW_STEP
+        g = grid((B, 2, Hf, Wf), gg[0], gg[1], torch.Generator().manual_seed(seed_of('blendg', shape))).numpy()
+    else:
+        f0, g = 3.0 * rng.standard_normal((B, 2, Hf, Wf)), rng.standard_normal((B, 2, Hf, Wf))
+    scale = (Wf / w, Hf / h)
+    xo = np.zeros((B, 3, h, w))
+    xo[:, :2] = _blend_flows(rng, B, h, w, dyadic, scale)
+    xo[:, 2] = rng.choice(BLEND_LOGITS, (B, h, w)) if dyadic or regime == 'final' else np.sqrt(2.0) * rng.standard_normal((B, h, w))
+    if regime == 'nonfinite':
+        xo[0, 0, h // 2, w // 2], xo[B - 1, 1, h // 2, 0] = np.nan, np.inf
+    xo = _to_dtype(xo, dtype)
+    inter, m, m32 = blend_inter(xo, Hf, Wf)
+    if dyadic:
+        m = sigmoid_of_exact_logits(xo[:, 2])
+        m32 = m.astype(np.float32)
+    t = taps32(inter, Hf, Wf)
+    c = dict(flow_init=f0.astype(np.float32), x_out=xo, g=g.astype(np.float32), inter=inter, m=m, m32=m32, t=t, shape=shape, lo=(h, w), regime=regime)
+    if dyadic:
+        blend_guard(c)
+    if regime == 'final':
+        blend_final_guard(c)
+    return c
+
+
+def blend_guard(c):
+    """The dyadic regime's conditions: sampling_guard's (dyadic sizes, flows on the 1/8 grid, taps32 == taps64, weights multiples of
+    1/64), flow_init on the 1/8 grid within +-4, grad_out on the fp16 gy grid, m in {0.5, 1, 0}, position factors exactly 1 (0 for a size
+    of 1).  Every product w v (1 - m), v a g, g (f - warped) m (1 - m) is then a multiple of 2^-14 far below 2^24 quanta."""
+    B, Hf, Wf = c['shape']
+    sampling_guard(c['flow_init'] * 0.0, c['g'], c['inter'], c['t'], torch.float16)
+    assert on_grid(torch.from_numpy(c['flow_init']), FLOW_STEP) and float(np.abs(c['flow_init']).max()) <= 4.0
+    assert blend_pos_factor(Wf) == (1.0 if Wf > 1 else 0.0) and blend_pos_factor(Hf) == (1.0 if Hf > 1 else 0.0)
+    top = 2 * 4 * 4.0 * GRIDS[torch.float16]['gy'][1] / 2.0 ** -14
+    assert top < LIMIT
+    return top
+
+
+def blend_final_guard(c, ulps=8):
+    """Final level: every modelled sampling position is at least `ulps` ulp away from an integer (so no rounding of the position
+    chain can move a tap), unless it lies more than one pixel outside the image."""
+    B, Hf, Wf = c['shape']
+    for key, size in (('ix', Wf), ('iy', Hf)):
+        p = c['t'][key].astype(np.float64)
+        near = (p > -1.5) & (p < size + 0.5)
+        dist = np.abs(p - np.rint(p))[near]
+        ulp = np.spacing(np.abs(c['t'][key]).astype(np.float32)).astype(np.float64)[near]
+        assert np.all(dist >= ulps * ulp), '%s: a position within %d ulp of an integer' % (key, ulps)
+
+
+def blend_final_backward_ref(c):
+    """Final level: the full-resolution gradients of blend_backward_ref (the flow channels times fp32(Wf / w), fp32(Hf / h): one more
+    rounding) through the exact adjoint of the resize (C = 3, no rate), the logit channel times s (1 - s) of the exact sigmoid values.
+    -> (g_x_out fp64 [B,3,h,w], bound): the per-pixel bounds carried through the adjoint's absolute weights, plus the resize kernels'
+    own gamma_(nnz + tree depth + 2) on the absolute terms (tests/test_hip_resize_exact.py's count)."""
+    B, Hf, Wf = c['shape']
+    h, w = c['lo']
+    full, b_full = blend_backward_ref(c['flow_init'], c['g'], c['t'], c['m'])
+    rate = np.array([float(np.float32(Wf / w)), float(np.float32(Hf / h)), 1.0]).reshape(1, 3, 1, 1)
+    full = full * rate
+    b_full = b_full * rate + U32 * np.abs(full)
+    gx, ga, nnz = resize_backward_ref(full, h, w, False)
+    carried = resize_backward_ref(b_full, h, w, False)[1]
+    bound = carried + gamma(nnz + RESIZE_TREE_DEPTH + 2)[None, None] * (ga + carried)
+    s = sigmoid_of_exact_logits(c['x_out'][:, 2])
+    gx[:, 2] *= s * (1.0 - s)
+    bound[:, 2] = bound[:, 2] * s * (1.0 - s) + 2 * U32 * np.abs(gx[:, 2])
+    return gx, bound

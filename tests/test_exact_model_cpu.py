@@ -3,7 +3,9 @@ test): the guard holds for every case list, torch's fp32 kernels in their own su
 bit (the order independence the GPU file relies on), the operands make enough outputs round / tie / hit zero for bit equality to
 mean something, and the fp16 range cases are what they claim to be.  The last section does the same for the sampling model
 (tests/test_hip_warp_exact.py, tests/test_hip_resize_exact.py): the fp32 position chain against the golden mask bits, the guards of
-the dyadic regime, the caps of the general one, route coverage, and what each backward case claims to contain."""
+the dyadic regime, the caps of the general one, route coverage, and what each backward case claims to contain — and for the
+normalisation, blend, occlusion and census models (tests/test_hip_norm_exact.py, tests/test_hip_blend_exact.py): route names, caps,
+counts, the NaN pixel of the occlusion oracle, the census adjoint against fp64 autograd."""
 import glob
 import os
 
@@ -529,3 +531,198 @@ def test_dyadic_resize_cases_keep_their_guard_and_general_ones_are_general():
     gx, _, _ = em.resize_backward_ref(gy, 4, 13, True)
     a, b = float((y * gy).sum()), float((gx * x).sum())
     assert abs(a - b) <= 1e-10 * max(1.0, abs(a))
+
+
+# ---- normalisation, SGU blend, occlusion check, census (tests/test_hip_norm_exact.py, tests/test_hip_blend_exact.py) ---------------------
+def _norm_routes():
+    for name in em.NORM_CASES:
+        for dtype in em.norm_dtypes(name):
+            c = em.norm_case(name, dtype)
+            yield name, dtype, c, em.normalize_route(c['N'], c['HW'], dtype, aligned=not c['misalign'])
+
+
+def test_normalize_route_names_every_case():
+    """normalize_route on the issue's table: the route each case was chosen for, and every (form, segmented, vec, ragged) combination
+    the host code can produce (wave rows are never segmented; a ragged last segment has an odd-length row behind it, never vectors for
+    16-bit types) has a case."""
+    r = {(n, em.SAMP_NAMES[d]): route for n, d, _, route in _norm_routes()}
+    assert r['hw2', 'bf16'] == ('wave', 1, 2, False) and r['hw63_9rows', 'fp16'] == ('wave', 1, 63, False)
+    assert r['hw64', 'bf16'] == ('wave', 1, 64, True) and r['hw64_misaligned', 'bf16'] == ('wave', 1, 64, False)
+    assert r['hw64', 'fp32'] == ('block', 1, 64, True) and r['hw64_misaligned', 'fp32'] == ('block', 1, 64, False)
+    assert r['wave_limit', 'fp16'] == ('wave', 1, 4096, True) and r['block_4104', 'fp16'] == ('block', 1, 4104, True)
+    assert r['seg2_2048', 'bf16'] == ('block', 2, 2048, True) and r['seg2_2048', 'fp32'] == ('block', 2, 2048, True)
+    assert r['seg2_2052', 'fp32'] == ('block', 2, 2052, True) and r['seg2_2052', 'fp16'] == ('block', 2, 2052, False)
+    assert r['seg2_ragged', 'bf16'] == ('block', 2, 2105, False) and 2 * 2105 > 61 * 69
+    assert r['seg4_ragged', 'fp32'] == ('block', 4, 2071, False) and 91 * 91 - 3 * 2071 == 2068
+    assert r['spike_wave', 'bf16'][0] == 'wave' and r['spike_block', 'fp16'] == ('block', 8, 3584, True)
+    assert em.NORM_CASES['hw63_9rows'][0][0] * em.NORM_CASES['hw63_9rows'][0][1] == 9            # a second workgroup with one live wave
+    assert max(c['N'] * c['HW'] for _, _, c, _ in _norm_routes()) == 2 * 256 * 57 * 72                   # 2.1 M elements: the largest operand
+    # every combination the host code can produce over a sweep of sizes ...
+    reach = set()
+    for dtype in em.SAMP_DTYPES:
+        for N in (1, 2, 3, 9, 64, 512, 600):
+            for HW in list(range(1, 70)) + list(range(4090, 4110)) + list(range(4200, 4216)) + list(range(8270, 8290)) + [28672, 172800]:
+                for aligned in (True, False):
+                    form, nseg, seglen, vec = em.normalize_route(N, HW, dtype, aligned)
+                    reach.add((dtype == em.F32, form, nseg > 1, vec, nseg * seglen != HW))
+    have = {(d == em.F32, route[0], route[1] > 1, route[3], route[1] * route[2] != c['HW']) for _, d, c, route in _norm_routes()}
+    assert have == reach, sorted(reach - have)
+
+
+def norm_share_cap(route, dtype):
+    """The cap on the share of elements of y with two 16-bit candidates: 1 %.  The bound of y is at least gamma_k (kappa |y| +
+    E|x - K| / std) and an fp16 value has 2^-11 |y| ... 2^-10 |y| to its neighbour, so for segments of 2048 elements and more (k >= 18) the interval of the bound itself spans more than 1 % of fp16's spacing whatever the data: there the cap is the ceiling
+    2 * 2^11 gamma_k (kappa + 2) of that ratio for |y| >= 1/2, and the bit-for-bit check of y against the returned statistics
+    (tests/test_hip_norm_exact.py) is what keeps those values sharp."""
+    k = em.norm_roundings(route, dtype)
+    if dtype == torch.float16 and route[2] >= 2048:
+        return lambda kappa: 2 * 2.0 ** 11 * em.gamma(k) * (kappa + 2.0)
+    return lambda kappa: 0.01
+
+
+def test_normalize_caps_and_spikes():
+    for name, dtype, c, route in _norm_routes():
+        ref = em.norm_forward_ref(c['x'], route, dtype)
+        assert np.all(np.isfinite(ref['y'])) and np.all(ref['b_y'] >= 0)
+        if c['spike']:
+            assert ref['kappa'].min() > 1000 and ref['b_rstd'].max() < 0.05                # wide, as the pivot note says, and still a check
+            continue
+        assert ref['kappa'].max() < 100 if dtype != em.F32 else True
+        if dtype != em.F32:
+            share, cap = em.two_candidate_share(ref['y'], ref['b_y'], dtype), norm_share_cap(route, dtype)(float(ref['kappa'].max()))
+            assert share <= cap, (name, em.SAMP_NAMES[dtype], share, cap)
+            assert cap <= 0.01 or (dtype == torch.float16 and cap < 0.1)
+    for HW in em.NORM_BWD_HW:
+        for dtype in em.SAMP_DTYPES:
+            y, gy, r = em.norm_bwd_case(HW, dtype)
+            ref, bound = em.norm_backward_ref(y, gy, r)
+            assert np.all(bound > 0) and np.all(np.isfinite(ref))
+    assert 513 - em.NORM_NT == 1                                                          # one element in the second stride
+
+
+def test_normalize_reference_notices_the_mutations():
+    """Dropping the last element of a ragged segment, or merging with HW for HW - 1, moves the statistics by more than their bounds."""
+    for name in ('seg2_ragged', 'seg4_ragged'):
+        for dtype in em.SAMP_DTYPES:
+            c = em.norm_case(name, dtype)
+            route = em.normalize_route(c['N'], c['HW'], dtype)
+            ref = em.norm_forward_ref(c['x'], route, dtype)
+            x = c['x'].astype(np.float64)
+            short = np.delete(x, c['HW'] - 1, axis=1)
+            assert np.all(np.abs(short.mean(1) - ref['mean']) > ref['b_mean'])
+            biased = 1.0 / np.sqrt(((x - ref['mean'][:, None]) ** 2).sum(1) / c['HW'] + em.NORM_EPS)
+            assert np.all(np.abs(biased - ref['rstd']) / ref['rstd'] > ref['b_rstd'])
+
+
+BLEND_COUNT_KEYS = ('merged', 'refused_lane63', 'refused_address', 'refused_row_end', 'collisions', 'left', 'right', 'top', 'bottom', 'past_hw')
+
+
+@pytest.mark.parametrize('dtype', [pytest.param(d, id=em.SAMP_NAMES[d]) for d in em.BLEND_DTYPES])
+def test_blend_cases_hold_their_guards_and_counts(dtype):
+    """Every blend case builds (the dyadic and final-level guards run inside blend_case); per regime every count the backward claims
+    is > 0; the wide cases have all of them at once; the final level's resize-gradient routes are named."""
+    for regime, cases in (('dyadic', [(s, None) for s in em.BLEND_DYADIC]), ('general', [(s, None) for s in em.BLEND_GENERAL]),
+                          ('final', [((2,) + hi, lo) for lo, hi in em.BLEND_FINAL])):
+        total = dict.fromkeys(BLEND_COUNT_KEYS, 0)
+        for shape, lo in cases:
+            c = em.blend_case(shape, dtype, regime, lo)
+            n = em.blend_counts(c['t'], *shape)
+            for k in BLEND_COUNT_KEYS:
+                total[k] += n[k]
+            if shape[1] >= 9 and shape[2] > 64:
+                assert all(n[k] > 0 for k in BLEND_COUNT_KEYS), (shape, n)
+        assert all(total[k] > 0 for k in BLEND_COUNT_KEYS), (regime, total)
+    assert em.blend_counts(em.blend_case((2, 9, 29), dtype, 'general')['t'], 2, 9, 29)['past_hw'] == 2 * 256 - 261
+    routes = {em.upsample_bwd_route(lo[0], lo[1], hi[0], hi[1], 3 * 2) for lo, hi in em.BLEND_FINAL}
+    assert routes == {'group4', 'band'}, routes
+    for shape in em.BLEND_GENERAL:
+        c = em.blend_case(shape, dtype, 'nonfinite')
+        assert int((~np.isfinite(c['inter'])).sum()) == 2
+        fu, b = em.blend_forward_ref(c['flow_init'], c['t'], c['m'])
+        assert np.all(np.isfinite(fu)) and np.all(np.isfinite(b))                         # no NaN from an outside tap's weight
+
+
+def test_blend_fixed_point_model_equals_the_fp64_adjoint_in_the_dyadic_regime():
+    for dtype in em.BLEND_DTYPES:
+        for shape in em.BLEND_DYADIC:
+            c = em.blend_case(shape, dtype, 'dyadic')
+            t64 = em.taps64(c['inter'], shape[1], shape[2])
+            gx, _, _ = em.warp_backward_ref(c['flow_init'], c['g'] * (1.0 - c['m'])[:, None], t64, 'none')
+            want = gx + c['m'][:, None] * c['g']
+            assert np.array_equal(em.blend_ginit_model(c['g'], c['t'], c['m32']).astype(np.float64), want)
+            assert set(np.unique(c['m'])) <= {0.0, 0.5, 1.0} and len(np.unique(c['m'])) == 3 or shape == (2, 2, 2)
+            # a merge without the address comparison would move contributions: pairs that the comparison separates exist
+            assert em.blend_counts(c['t'], *shape)['refused_address'] > 0 or shape == (2, 2, 2)
+
+
+def test_occ_cases_counts_caps_and_the_nan_pixel():
+    from oracle import ops as oracle_ops
+    total = dict(consistent_in=0, inconsistent_in=0, outgoing=0, edge=0, nonfinite=0)
+    nan_in_frame = 0
+    for shape in em.OCC_DYADIC + em.OCC_GENERAL:
+        dyadic = shape in em.OCC_DYADIC
+        c = em.occ_case(shape, dyadic)
+        ref = em.occ_ref(c['ff'], c['fb'], *em.OCC_ALPHA)
+        n = em.occ_counts(c, ref)
+        for k in total:
+            total[k] += n[k]
+        if shape[1] > 1 and shape[2] > 1:
+            assert n['consistent_in'] > 0 and n['inconsistent_in'] > 0 and n['outgoing'] > 0 and n['edge'] > 0, (shape, n)
+        assert dyadic or n['nonfinite'] == 3
+        if not dyadic:
+            b, ch, i, j = em.nonfinite_places(*shape)[0]                                 # the NaN flow: never consistent, output 0 while in frame
+            assert np.isnan(c['ff'][b, ch, i, j]) and not ref[0][2][b, i, j] and ref[0][0][b, i, j] == (0.0 if ref[0][3][b, i, j] else 1.0)
+            nan_in_frame += int(ref[0][3][b, i, j])
+        for _, undecided, _, _ in ref:
+            assert undecided.mean() <= 0.01, (shape, undecided.mean())
+        # the oracle (torch, fp32) agrees with the step-by-step model wherever the comparison is decided — NaN flows included
+        o1, o2 = oracle_ops.occ_check(torch.from_numpy(c['ff']), torch.from_numpy(c['fb']), *em.OCC_ALPHA)
+        for o, (want, undecided, _, _) in zip((o1, o2), ref):
+            assert np.array_equal(o.numpy()[:, 0][~undecided], want[~undecided]), shape
+    assert all(v > 0 for v in total.values()) and nan_in_frame > 0, (total, nan_in_frame)
+    # '<=' for '<' in the threshold would show: dyadic pixels sit exactly on it
+    c = em.occ_case((2, 17, 65), True)
+    ref = em.occ_ref(c['ff'], c['fb'], *em.OCC_ALPHA)
+    assert sum(int(u.sum()) for _, u, _, _ in ref) > 0
+
+
+def test_oracle_occ_check_keeps_a_nan_flow_in_the_frame():
+    """utils/tools.py:663-667 starts from ones and zeroes px > W-1, px < 0, py > H-1, py < 0: a NaN position fails all four and stays in
+    the frame; its comparison with the threshold is false, so the pixel's output is 0."""
+    from oracle import ops as oracle_ops
+    ff, fb = torch.zeros(1, 2, 4, 5), torch.zeros(1, 2, 4, 5)
+    ff[0, 0, 1, 2] = float('nan')
+    o1, o2 = oracle_ops.occ_check(ff, fb)
+    assert float(o1[0, 0, 1, 2]) == 0.0 and float(o1.sum()) == 19.0 and float(o2[0, 0, 1, 2]) == 0.0
+    ff[0, 0, 1, 2] = 10.0                                                                 # leaves the frame: outgoing, 1
+    assert float(oracle_ops.occ_check(ff, fb)[0][0, 0, 1, 2]) == 1.0
+
+
+def test_census_model_is_the_adjoint_and_its_cases_are_what_they_claim():
+    for size in em.CENSUS_SIZES:
+        H, W = size
+        for R in em.CENSUS_R:
+            for kind in em.CENSUS_KINDS:
+                g1, g2, G = em.census_case(size, kind)
+                assert g1.min() >= 0 and g1.max() <= 1 and g2.min() >= 0 and g2.max() <= 1
+                ref = em.census_ref(g1, g2, G, R)
+                a, b = (torch.tensor(v, dtype=torch.float64, requires_grad=True) for v in (g1, g2))
+                pa, pb = F.pad(a, (R,) * 4), F.pad(b, (R,) * 4)
+                d = 0
+                for dy in range(2 * R + 1):
+                    for dx in range(2 * R + 1):
+                        u1, u2 = pa[:, dy:dy + H, dx:dx + W] - a, pb[:, dy:dy + H, dx:dx + W] - b
+                        t = u1 / torch.sqrt(em.CENSUS_A + u1 * u1) - u2 / torch.sqrt(em.CENSUS_A + u2 * u2)
+                        d = d + t * t / (em.CENSUS_B + t * t)
+                ga, gb = torch.autograd.grad(d, (a, b), torch.tensor(G, dtype=torch.float64))
+                assert np.allclose(d.detach().numpy(), ref['dist'], rtol=1e-12, atol=1e-14)
+                assert np.allclose(ga.numpy(), ref['gg1'], rtol=1e-9, atol=1e-12) and np.allclose(gb.numpy(), ref['gg2'], rtol=1e-9, atol=1e-12)
+                assert np.all(ref['b_dist'] <= 1e-4 * np.maximum(ref['dist'], 1e-3))       # the bounds stay a check: 1e-4 relative at most
+                if kind == 'equal':
+                    assert not ref['dist'].any() and not ref['gg1'].any() and not ref['gg2'].any()
+                if kind == 'constant' and H > 2 * R and W > 2 * R:
+                    assert np.all(g1[:, R:H - R, R:W - R] == g1[0, 0, 0])
+                if kind == 'random' and min(H, W) > 1:
+                    # the bound is a small fraction of the gradient: a missing family of terms (the neighbour role) cannot hide in it
+                    assert np.abs(ref['gg1']).max() > 100 * ref['b_gg1'].max()
+    assert 2 < 2 * min(em.CENSUS_R) + 1 and 17 * 65 > 256                                 # an image smaller than the window; two workgroups

@@ -60,7 +60,10 @@ void normalize_stats_kernel(const T* __restrict__ x, float* __restrict__ ws, int
   float mean, m2;
   if constexpr (sizeof(typename Elem<T>::store_t) == 2) {
     // 16-bit features: ONE sweep — sums of (x - K) and (x - K)^2 about a pivot K taken from the segment
-    // itself, so that M2 = s2 - s1^2/n loses at most a bit or two (far below the bf16/fp16 output rounding)
+    // itself (its first element).  M2 = s2 - s1^2/n then carries a relative error proportional to
+    // kappa = 1 + n (mean - K)^2 / M2: tiny (kappa of a few) when the first element is typical of the row, far below the
+    // bf16/fp16 output rounding; a first element many standard deviations off the row (kappa ~ 1e6 at 512 sigma) costs
+    // the standard deviation up to two bf16 ulps (INTEGRATION.md operand ranges)
     float s1 = 0.f, s2 = 0.f;
     float K;
     if (pitched) {
