@@ -707,6 +707,36 @@ int upf_grads_nonfinite_check(const upf_mt_launch* launch, int* flag, void* stre
  * written (parameters, both moments and the running maximum keep their bits). */
 int upf_adam_amsgrad_step(const upf_mt_launch* launch, const float* lr, const float* step, const float* loss_scale,
                           const int* flag, double beta1, double beta2, double eps, double weight_decay, void* stream);
+/* ---- a bound on the global gradient norm, and the norm as a statistic (torch.nn.utils.clip_grad_norm_, L2, inside the step).
+ * For ONE optimizer step over ALL launches of ALL parameter groups:
+ *   1. sumsq = sum of (double)g * (double)g over every gradient element, the gradients still multiplied by the loss scale S
+ *      (exact products; a sum of finite fp32 squares cannot overflow a double).  Accumulated in double in a FIXED order, no
+ *      atomics: each thread its strided elements in index order, a 256-wide tree through LDS, one partial per workgroup, then
+ *      the partials in index order by one workgroup and the same tree — the same bits run to run for the same addresses.
+ *   2. norm = (float)(sqrt(sumsq) / (double)S): the L2 norm of the UN-scaled gradients before clipping (S a power of two).
+ *   3. coef = (float)fmin((double)max_norm / ((double)norm + 1e-6), 1.0): evaluated in double from the fp32 norm and rounded
+ *      once, so a host reproduces it bit for bit from norm.  max_norm = +inf: coef == 1.0f exactly (measure only).
+ *   4. Adam reads g = grad * (1 / S); g = g * coef — two separately rounded fp32 multiplies — then weight decay and the rest as
+ *      upf_adam_amsgrad_step.  The gradient tensors themselves are NOT modified (unlike torch): the coefficient is folded into
+ *      the read.
+ *   5. The non-finite flag is raised in the same pass, exactly as upf_grads_nonfinite_check raises it, and norm is non-finite
+ *      IF AND ONLY IF the flag was raised (squares are >= 0: no inf - inf; finite squares cannot overflow).  On such a step
+ *      Adam writes nothing; coef is then unspecified and is read by nothing that writes.
+ *
+ * upf_grads_sumsq_check: upf_grads_nonfinite_check plus partials[b] = the sum of squares of workgroup b's chunk, for the
+ * launch's n_blocks workgroups (every one is written; 8-byte aligned device memory).  A step of several launches gives each
+ * its own range of one vector: the count is host arithmetic over the launch plan (the sum of n_blocks). */
+int upf_grads_sumsq_check(const upf_mt_launch* launch, double* partials /* n_blocks of them */, int* flag, void* stream);
+/* One workgroup: sumsq = partials[0..n_partials) summed in the fixed order above; norm_out[0], coef_out[0] (fp32 DEVICE
+ * scalars) as in 2. and 3. from the DEVICE scalar loss_scale[0].  UPF_EINVAL: a null pointer, n_partials <= 0, max_norm that is
+ * not positive (NaN included). */
+int upf_grad_norm_clip_coef(const double* partials, int n_partials, const float* loss_scale, float max_norm,
+                            float* norm_out, float* coef_out, void* stream);
+/* upf_adam_amsgrad_step with g = (grad / loss_scale[0]) * clip_coef[0] (4. above; clip_coef a DEVICE scalar, read only when
+ * flag[0] == 0).  clip_coef[0] == 1.0f gives the bits of upf_adam_amsgrad_step. */
+int upf_adam_amsgrad_step_clipped(const upf_mt_launch* launch, const float* lr, const float* step, const float* loss_scale,
+                                  const float* clip_coef, const int* flag, double beta1, double beta2, double eps,
+                                  double weight_decay, void* stream);
 /* The end of a step, one thread (torch.amp.GradScaler.update with a floor):
  *   flag set:   loss_scale = max(loss_scale * backoff_factor, 1), growth_tracker = 0, skipped_steps += 1
  *   flag clear: steps[0..nsteps) += 1 (the step counters of the parameter groups), growth_tracker += 1, and when it reaches

@@ -108,6 +108,9 @@ SIGNATURES = {
     'upf_occ_check': [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp],
     'upf_grads_nonfinite_check': [_vp, _vp, _vp],
     'upf_adam_amsgrad_step': [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp],
+    'upf_grads_sumsq_check': [_vp, _vp, _vp, _vp],
+    'upf_grad_norm_clip_coef': [_vp, _i, _vp, _f, _vp, _vp, _vp],
+    'upf_adam_amsgrad_step_clipped': [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp],
     'upf_loss_scale_update': [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp],
     'upf_frames_u8_assemble': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp],
     'upf_frames_u8_stack16': [_vp, _vp, _vp, _vp, _i, _ll, _ll, _vp, _i, _ll, _ll, _i, _i, _i, _d, _d, _d, _d, _vp],

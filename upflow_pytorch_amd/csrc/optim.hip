@@ -1,6 +1,8 @@
 // Device-side optimiser step of the training loop: non-finite check of the gradients, Adam (amsgrad, L2 weight decay) with the
 // loss scale divided out as the gradient is read, and the dynamic loss-scale state machine — all on the stream, no host
 // synchronisation, so the whole of it is captured into the training step's hipGraph (include/upflow_hip.h has the contract).
+// With a bound on the global gradient norm the check pass also takes the sum of squares (double, one partial per workgroup, a
+// fixed-order finish: no atomics, the same bits run to run) and Adam multiplies the clip coefficient in where it reads the gradient.
 //
 // Multi-tensor launches: the tensors' addresses travel BY VALUE in the kernel arguments (upf_mt_launch, < 4 KB): the
 // gradients of a captured step are allocated during the capture, and a host-to-device copy of a pointer table cannot be
@@ -48,15 +50,80 @@ __global__ __launch_bounds__(NT) void nonfinite_kernel(const upf_mt_launch L, in
   if (bad) *flag = 1;
 }
 
+// ---- 1b. the same pass with the sum of squares: partials[b] = sum over workgroup b's chunk of (double)g * (double)g ---------
+// (the product of two fp32 values is exact in double; squares are >= 0 and a finite fp32 square is < 2^256, so the sum is
+// non-finite if and only if an element is — the same condition the flag reports)
+__device__ __forceinline__ double block_sum(double acc, double* s_red) {
+  s_red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = NT / 2; w > 0; w >>= 1) {                     // a fixed tree: the order does not depend on timing
+    if ((int)threadIdx.x < w) s_red[threadIdx.x] = s_red[threadIdx.x] + s_red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return s_red[0];
+}
+
+__global__ __launch_bounds__(NT) void sumsq_check_kernel(const upf_mt_launch L, double* __restrict__ partials, int* __restrict__ flag) {
+  __shared__ double s_red[NT];
+  const int b = blockIdx.x;
+  const int t = L.block_tensor[b];
+  const long long first = (long long)L.block_chunk[b] * UPF_MT_CHUNK;
+  const int n = (int)min((long long)UPF_MT_CHUNK, (long long)L.numel[t] - first);
+  const float* __restrict__ g = (const float*)L.grad[t] + first;
+  int bad = 0;
+  int done = 0;
+  double acc = 0.0;
+  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+    const int n4 = n >> 2;
+    const float4* __restrict__ g4 = (const float4*)g;
+    for (int i = threadIdx.x; i < n4; i += NT) {
+      const float4 v = g4[i];
+      bad |= nonfinite(v.x) | nonfinite(v.y) | nonfinite(v.z) | nonfinite(v.w);
+      acc += (double)v.x * (double)v.x;
+      acc += (double)v.y * (double)v.y;
+      acc += (double)v.z * (double)v.z;
+      acc += (double)v.w * (double)v.w;
+    }
+    done = n4 << 2;
+  }
+  for (int i = done + threadIdx.x; i < n; i += NT) {
+    const float v = g[i];
+    bad |= nonfinite(v);
+    acc += (double)v * (double)v;
+  }
+  if (bad) *flag = 1;
+  const double total = block_sum(acc, s_red);
+  if (threadIdx.x == 0) partials[b] = total;
+}
+
+// ---- 1c. one workgroup: the partials in index order -> norm of the UN-scaled gradients, clip coefficient ------------------
+__global__ __launch_bounds__(NT) void norm_finish_kernel(const double* __restrict__ partials, int n_partials,
+                                                         const float* __restrict__ scale_p, float max_norm,
+                                                         float* __restrict__ norm_out, float* __restrict__ coef_out) {
+  __shared__ double s_red[NT];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_partials; i += NT) acc += partials[i];
+  const double sumsq = block_sum(acc, s_red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)(sqrt(sumsq) / (double)scale_p[0]);            // (S a power of two: the division is exact)
+    norm_out[0] = norm;
+    coef_out[0] = (float)fmin((double)max_norm / ((double)norm + 1e-6), 1.0);  // torch's max_norm / (total_norm + 1e-6), clamped
+  }
+}
+
 // ---- 2. Adam + amsgrad + L2 weight decay (torch/optim/adam.py, the capturable form) -----------------------------------------
 struct Hyper {
   double beta1, beta2, eps, weight_decay;
 };
+static_assert(sizeof(upf_mt_launch) + sizeof(Hyper) + 5 * sizeof(void*) <= 4096, "the clipped Adam launch: table, Hyper, five pointers");
 
 // one element; lr, bc1, bc2_sqrt as torch's kernel holds them (lr double from the device float, the corrections fp32)
+// CLIP: the gradient is multiplied by the clip coefficient after the un-scaling (two separately rounded fp32 multiplies)
+template <bool CLIP>
 __device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float& vmax, const Hyper& h, float inv_scale,
-                                             double lr, float bc1, float bc2_sqrt) {
+                                             float coef, double lr, float bc1, float bc2_sqrt) {
   g = g * inv_scale;                                        // (a power of two: exact)
+  if (CLIP) g = g * coef;
   if (h.weight_decay != 0.0) g = (float)(g + p * h.weight_decay);
   const double w = 1.0 - h.beta1;                           // lerp(m, g, 1 - beta1)
   m = w < 0.5 ? (float)(m + w * (g - m)) : (float)(g - (g - m) * (1.0 - w));
@@ -67,9 +134,11 @@ __device__ __forceinline__ void adam_element(float& p, float g, float& m, float&
   p = p - step_size * m / denom;
 }
 
-__global__ __launch_bounds__(NT) void adam_kernel(const upf_mt_launch L, const Hyper h, const float* __restrict__ lr_p,
-                                                  const float* __restrict__ step_p, const float* __restrict__ scale_p,
-                                                  const int* __restrict__ flag) {
+// the body of both Adam kernels; coef_p is read when CLIP only (the unclipped launch does not carry it)
+template <bool CLIP>
+__device__ __forceinline__ void adam_body(const upf_mt_launch& L, const Hyper& h, const float* __restrict__ lr_p,
+                                          const float* __restrict__ step_p, const float* __restrict__ scale_p,
+                                          const float* __restrict__ coef_p, const int* __restrict__ flag) {
   // a non-finite gradient anywhere: this step changes nothing (the flag is uniform over the grid: the check ran before, the
   // state machine that clears it runs after)
   if (*flag != 0) return;
@@ -84,6 +153,7 @@ __global__ __launch_bounds__(NT) void adam_kernel(const upf_mt_launch L, const H
   const float bc1 = s_bc[0], bc2_sqrt = s_bc[1];
   const double lr = (double)lr_p[0];
   const float inv_scale = 1.f / scale_p[0];
+  const float coef = CLIP ? coef_p[0] : 1.f;                // (read only behind the flag: unspecified on a non-finite step)
 
   const int b = blockIdx.x;
   const int t = L.block_tensor[b];
@@ -102,10 +172,10 @@ __global__ __launch_bounds__(NT) void adam_kernel(const upf_mt_launch L, const H
     for (int i = threadIdx.x; i < n4; i += NT) {
       float4 P = ((float4*)p)[i], M = ((float4*)m)[i], V = ((float4*)v)[i], X = ((float4*)x)[i];
       const float4 G = ((const float4*)g)[i];
-      adam_element(P.x, G.x, M.x, V.x, X.x, h, inv_scale, lr, bc1, bc2_sqrt);
-      adam_element(P.y, G.y, M.y, V.y, X.y, h, inv_scale, lr, bc1, bc2_sqrt);
-      adam_element(P.z, G.z, M.z, V.z, X.z, h, inv_scale, lr, bc1, bc2_sqrt);
-      adam_element(P.w, G.w, M.w, V.w, X.w, h, inv_scale, lr, bc1, bc2_sqrt);
+      adam_element<CLIP>(P.x, G.x, M.x, V.x, X.x, h, inv_scale, coef, lr, bc1, bc2_sqrt);
+      adam_element<CLIP>(P.y, G.y, M.y, V.y, X.y, h, inv_scale, coef, lr, bc1, bc2_sqrt);
+      adam_element<CLIP>(P.z, G.z, M.z, V.z, X.z, h, inv_scale, coef, lr, bc1, bc2_sqrt);
+      adam_element<CLIP>(P.w, G.w, M.w, V.w, X.w, h, inv_scale, coef, lr, bc1, bc2_sqrt);
       ((float4*)p)[i] = P;
       ((float4*)m)[i] = M;
       ((float4*)v)[i] = V;
@@ -115,12 +185,25 @@ __global__ __launch_bounds__(NT) void adam_kernel(const upf_mt_launch L, const H
   }
   for (int i = done + threadIdx.x; i < n; i += NT) {
     float P = p[i], M = m[i], V = v[i], X = x[i];
-    adam_element(P, g[i], M, V, X, h, inv_scale, lr, bc1, bc2_sqrt);
+    adam_element<CLIP>(P, g[i], M, V, X, h, inv_scale, coef, lr, bc1, bc2_sqrt);
     p[i] = P;
     m[i] = M;
     v[i] = V;
     x[i] = X;
   }
+}
+
+__global__ __launch_bounds__(NT) void adam_kernel(const upf_mt_launch L, const Hyper h, const float* __restrict__ lr_p,
+                                                  const float* __restrict__ step_p, const float* __restrict__ scale_p,
+                                                  const int* __restrict__ flag) {
+  adam_body<false>(L, h, lr_p, step_p, scale_p, nullptr, flag);
+}
+
+// (one more pointer in the argument block: 3400 + 32 + 5 * 8 bytes, inside the static_assert above)
+__global__ __launch_bounds__(NT) void adam_clipped_kernel(const upf_mt_launch L, const Hyper h, const float* __restrict__ lr_p,
+                                                          const float* __restrict__ step_p, const float* __restrict__ scale_p,
+                                                          const float* __restrict__ coef_p, const int* __restrict__ flag) {
+  adam_body<true>(L, h, lr_p, step_p, scale_p, coef_p, flag);
 }
 
 // ---- 3. the loss-scale state machine (torch.amp.GradScaler.update, with a floor of 1), one thread ------------------------
@@ -193,6 +276,41 @@ extern "C" int upf_adam_amsgrad_step(const upf_mt_launch* launch, const float* l
   hipLaunchKernelGGL(optim::adam_kernel, dim3(launch->n_blocks), dim3(optim::NT), 0, (hipStream_t)stream, *launch, h, lr, step,
                      loss_scale, flag);
   return check_launch("adam_amsgrad_step");
+}
+
+extern "C" int upf_grads_sumsq_check(const upf_mt_launch* launch, double* partials, int* flag, void* stream) {
+  using namespace upf;
+  UPF_REQUIRE(partials && flag, UPF_EINVAL, "grads_sumsq_check: null pointer");
+  UPF_REQUIRE(aligned_to(partials, 8), UPF_EINVAL, "grads_sumsq_check: partials not 8-byte aligned");
+  if (int rc = optim::check_plan(launch, "grads_sumsq_check", false)) return rc;
+  hipLaunchKernelGGL(optim::sumsq_check_kernel, dim3(launch->n_blocks), dim3(optim::NT), 0, (hipStream_t)stream, *launch, partials,
+                     flag);
+  return check_launch("grads_sumsq_check");
+}
+
+extern "C" int upf_grad_norm_clip_coef(const double* partials, int n_partials, const float* loss_scale, float max_norm,
+                                       float* norm_out, float* coef_out, void* stream) {
+  using namespace upf;
+  UPF_REQUIRE(partials && loss_scale && norm_out && coef_out, UPF_EINVAL, "grad_norm_clip_coef: null pointer");
+  UPF_REQUIRE(n_partials > 0, UPF_EINVAL, "grad_norm_clip_coef: %d partials", n_partials);
+  UPF_REQUIRE(max_norm > 0.f, UPF_EINVAL, "grad_norm_clip_coef: max_norm must be positive (+inf: measure only)");
+  hipLaunchKernelGGL(optim::norm_finish_kernel, dim3(1), dim3(optim::NT), 0, (hipStream_t)stream, partials, n_partials, loss_scale,
+                     max_norm, norm_out, coef_out);
+  return check_launch("grad_norm_clip_coef");
+}
+
+extern "C" int upf_adam_amsgrad_step_clipped(const upf_mt_launch* launch, const float* lr, const float* step, const float* loss_scale,
+                                             const float* clip_coef, const int* flag, double beta1, double beta2, double eps,
+                                             double weight_decay, void* stream) {
+  using namespace upf;
+  UPF_REQUIRE(lr && step && loss_scale && clip_coef && flag, UPF_EINVAL, "adam_amsgrad_step_clipped: null pointer");
+  UPF_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0, UPF_EINVAL,
+              "adam_amsgrad_step_clipped: betas in [0, 1), eps and weight_decay >= 0");
+  if (int rc = optim::check_plan(launch, "adam_amsgrad_step_clipped", true)) return rc;
+  const optim::Hyper h{beta1, beta2, eps, weight_decay};
+  hipLaunchKernelGGL(optim::adam_clipped_kernel, dim3(launch->n_blocks), dim3(optim::NT), 0, (hipStream_t)stream, *launch, h, lr, step,
+                     loss_scale, clip_coef, flag);
+  return check_launch("adam_amsgrad_step_clipped");
 }
 
 extern "C" int upf_loss_scale_update(float* loss_scale, int* growth_tracker, int* skipped_steps, int* flag, float* steps, int nsteps,

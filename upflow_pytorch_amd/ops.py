@@ -2452,11 +2452,18 @@ def mt_plan(sizes, max_tensors=MT_TENSORS, max_blocks=MT_BLOCKS, chunk=MT_CHUNK)
     return launches
 
 
-def mt_kernarg_bytes():
+def mt_kernarg_bytes(clipped=False):
     """Bytes of the largest argument block of the multi-tensor kernels (the Adam launch: the table, four double
-    hyper-parameters, four pointers)."""
+    hyper-parameters, four pointers; clipped=True: the clipped Adam launch, the larger of the two — one more pointer, the clip
+    coefficient)."""
     import ctypes
-    return ctypes.sizeof(_lib.MtLaunch) + 4 * 8 + 4 * 8
+    return ctypes.sizeof(_lib.MtLaunch) + 4 * 8 + (5 if clipped else 4) * 8
+
+
+def mt_partials(sizes):
+    """The number of workgroups — one fp64 partial each in grads_sumsq_check — that mt_plan gives a tensor list: the sum of
+    ceil(n / MT_CHUNK).  Pure host arithmetic."""
+    return sum(len(blocks) for _, blocks in mt_plan(sizes))
 
 
 class MtTables():
@@ -2476,6 +2483,7 @@ class MtTables():
             self.launches.append((L, tensors))
         self.device = None
         self.filled = set()
+        self.n_blocks = sum(L.n_blocks for L, _ in self.launches)     # (all launches: the partials of grads_sumsq_check)
 
     def set(self, which, tensors):
         """which: 'param' | 'grad' | 'exp_avg' | 'exp_avg_sq' | 'max_exp_avg_sq'; tensors: fp32, contiguous, on one GPU, of
@@ -2513,16 +2521,54 @@ def grads_nonfinite_check(tables, flag):
         _lib.call('upf_grads_nonfinite_check', ctypes.byref(L), f, _lib.stream_ptr(tables.device))
 
 
-def adam_amsgrad_step(tables, lr, step, loss_scale, flag, beta1, beta2, eps, weight_decay):
+def grads_sumsq_check(tables, partials, flag):
+    """grads_nonfinite_check plus the sum of squares of the gradients (still multiplied by the loss scale), in double: every
+    launch of `tables` writes one partial per workgroup at its own running offset into `partials`, an fp64 device vector of at
+    least tables.n_blocks elements (a view into a longer vector when a step has several tables); fixed order, no atomics.
+    -> the number of partials written."""
+    import ctypes
+    if 'grad' not in tables.filled:
+        raise UpflowHipError('grads_sumsq_check: the gradients were not set')
+    f = _mt_scalar(flag, torch.int32, 'flag')
+    base = _mt_scalar(partials, torch.float64, 'partials')
+    if partials.numel() < tables.n_blocks:
+        raise UpflowHipError('grads_sumsq_check: %d partials for %d workgroups' % (partials.numel(), tables.n_blocks))
+    if partials.device != tables.device:
+        raise UpflowHipError('operands on different devices: %s vs %s' % (tables.device, partials.device))
+    off = 0
+    for L, _ in tables.launches:
+        _lib.call('upf_grads_sumsq_check', ctypes.byref(L), ctypes.c_void_p(base.value + 8 * off), f, _lib.stream_ptr(tables.device))
+        off += L.n_blocks
+    return off
+
+
+def grad_norm_clip_coef(partials, loss_scale, max_norm, norm_out, coef_out):
+    """One workgroup: norm_out = (float)(sqrt(sum of `partials`, in index order) / loss_scale) — the L2 norm of the un-scaled
+    gradients before clipping — and coef_out = (float)min(max_norm / (norm_out + 1e-6), 1) in double; max_norm=inf: exactly 1.
+    partials fp64, the others fp32 device scalars.  A non-finite gradient makes norm_out non-finite and coef_out unspecified."""
+    args = (_mt_scalar(partials, torch.float64, 'partials'), int(partials.numel()), _mt_scalar(loss_scale, torch.float32, 'loss_scale'),
+            float(max_norm), _mt_scalar(norm_out, torch.float32, 'norm_out'), _mt_scalar(coef_out, torch.float32, 'coef_out'))
+    _lib.check_gpu(partials, loss_scale, norm_out, coef_out)
+    _lib.call('upf_grad_norm_clip_coef', *args, _lib.stream_ptr(partials.device))
+
+
+def adam_amsgrad_step(tables, lr, step, loss_scale, flag, beta1, beta2, eps, weight_decay, clip_coef=None):
     """torch.optim.Adam(amsgrad=True) with L2 weight decay on the tensors of `tables`, in place; lr, step (the count BEFORE
-    this step; not advanced here), loss_scale (fp32) and flag (int32) are device scalars; flag != 0: nothing is written."""
+    this step; not advanced here), loss_scale (fp32) and flag (int32) are device scalars; flag != 0: nothing is written.
+    clip_coef: None, or an fp32 device scalar the un-scaled gradient is multiplied by as it is read (the gradient tensors are not
+    modified); read only when flag == 0."""
     import ctypes
     if tables.filled != set(_MT_LISTS):
         raise UpflowHipError('adam_amsgrad_step: lists not set: %s' % sorted(set(_MT_LISTS) - tables.filled))
     args = (_mt_scalar(lr, torch.float32, 'lr'), _mt_scalar(step, torch.float32, 'step'),
-            _mt_scalar(loss_scale, torch.float32, 'loss_scale'), _mt_scalar(flag, torch.int32, 'flag'))
+            _mt_scalar(loss_scale, torch.float32, 'loss_scale'))
+    if clip_coef is not None:
+        name, args = 'upf_adam_amsgrad_step_clipped', args + (_mt_scalar(clip_coef, torch.float32, 'clip_coef'),)
+    else:
+        name = 'upf_adam_amsgrad_step'
+    args = args + (_mt_scalar(flag, torch.int32, 'flag'),)
     for L, _ in tables.launches:
-        _lib.call('upf_adam_amsgrad_step', ctypes.byref(L), *args, float(beta1), float(beta2), float(eps), float(weight_decay),
+        _lib.call(name, ctypes.byref(L), *args, float(beta1), float(beta2), float(eps), float(weight_decay),
                   _lib.stream_ptr(tables.device))
 
 

@@ -10,11 +10,15 @@ optimizer, and the Trainer's whole step is one hipGraph.
     loss.backward(gradient=opt.loss_scale)          # the device scalar S seeds the backward pass: no extra multiply
     opt.step()                                      # check, (un-scaled) Adam or nothing, S update
 
+max_grad_norm=M adds what torch.nn.utils.clip_grad_norm_ does, inside the same step: the check's pass also takes the global sum of
+squares, and Adam reads grad / S * min(M / (norm + 1e-6), 1); opt.grad_norm is the pre-clip norm as a device scalar.
+
 state_dict() has torch.optim.Adam's layout (state keys step / exp_avg / exp_avg_sq / max_exp_avg_sq, the same param_groups
 entries), so a checkpoint moves between the two in both directions; the scale's own state travels separately
 (scaler_state_dict), as a GradScaler's does.
 """
 import math
+import numbers
 
 import torch
 
@@ -38,16 +42,36 @@ def parse_loss_scale(loss_scale):
     return s, False
 
 
+def parse_max_grad_norm(max_grad_norm):
+    """-> None, or the bound as a python float: a positive number or math.inf (measure the norm, clip nothing); anything else —
+    <= 0, NaN, a non-number — is a ValueError."""
+    if max_grad_norm is None:
+        return None
+    if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, numbers.Real) or not float(max_grad_norm) > 0.0:
+        raise ValueError('max_grad_norm must be None, a positive number or math.inf, got %r' % (max_grad_norm,))
+    return float(max_grad_norm)
+
+
 class NativeAdam(torch.optim.Optimizer):
     """torch.optim.Adam(amsgrad=True, weight_decay=L2) whose step is three kernel families on the current stream — no host
     synchronisation, no .item() — with a loss scale:
         loss_scale   'dynamic' (starts at 2^16, halves on a non-finite step, never below 1, doubles after growth_interval clean
                      steps), or a fixed power of two (default 1.0: plain Adam that skips non-finite steps)
-    Device tensors: loss_scale (fp32, the seed for loss.backward), skipped_steps, growth_tracker (int32).
+        max_grad_norm  None (default): the step above, launch for launch.  A positive float: the global L2 norm of the UN-scaled
+                     gradients of ALL groups is bounded as torch.nn.utils.clip_grad_norm_ bounds it — coef = min(max_grad_norm /
+                     (norm + 1e-6), 1) — inside the step: the non-finite pass also takes the sum of squares (double, fixed order, no
+                     atomics: reproducible), one workgroup turns it into `grad_norm` and `clip_coef`, and Adam multiplies the
+                     coefficient in where it reads the gradient.  p.grad itself is NOT modified, unlike torch: the coefficient is
+                     folded into the read.  math.inf: the norm is measured, nothing is clipped (clip_coef == 1 exactly).  On a
+                     non-finite step grad_norm is non-finite (if and only if) and clip_coef is unspecified.  No state: state_dict()
+                     is unchanged.
+    Device tensors: loss_scale (fp32, the seed for loss.backward), skipped_steps, growth_tracker (int32); with max_grad_norm
+    grad_norm (fp32: the pre-clip norm of the un-scaled gradients of the last step) and clip_coef (fp32).
     lr may be a python float or a device tensor (graph capture: a tensor, updated in place by the schedulers)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=True, *, loss_scale=1.0,
-                 growth_interval=2000, growth_factor=2.0, backoff_factor=0.5):
+                 growth_interval=2000, growth_factor=2.0, backoff_factor=0.5, max_grad_norm=None):
+        max_grad_norm = parse_max_grad_norm(max_grad_norm)
         if not amsgrad:
             raise ValueError('NativeAdam implements the amsgrad variant only (scripts/simple_train.py:121)')
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and eps >= 0.0 and weight_decay >= 0.0):
@@ -78,6 +102,11 @@ class NativeAdam(torch.optim.Optimizer):
         self._steps = torch.zeros(len(self.param_groups), dtype=torch.float32, device=dev)   # one counter per group
         self._lr_dev = [None] * len(self.param_groups)                          # (device copies of python-float learning rates)
         self._tables = {}
+        self.max_grad_norm = max_grad_norm
+        if max_grad_norm is not None:
+            self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            self.clip_coef = torch.ones((), dtype=torch.float32, device=dev)
+            self._partials = None                                # (fp64, one per workgroup of all groups: made with the tables)
 
     def add_param_group(self, group):
         super().add_param_group(group)
@@ -173,12 +202,32 @@ class NativeAdam(torch.optim.Optimizer):
         work = [w for w in work if w[2] is not None]
         if not work:
             return None
+        if self.max_grad_norm is not None:
+            return self._clipped_step(work)
         for _, _, t in work:                                   # 1. ANY non-finite gradient of ANY group skips the whole step
             ops.grads_nonfinite_check(t, self._flag)
         for gi, g, t in work:                                  # 2. the update, or nothing
             ops.adam_amsgrad_step(t, self._lr_tensor(gi, g), self._steps[gi], self.loss_scale, self._flag, g['betas'][0],
                                   g['betas'][1], g['eps'], g['weight_decay'])
         # 3. step counters, scale, tracker, skipped count; clears the flag
+        ops.loss_scale_update(self.loss_scale, self.growth_tracker, self.skipped_steps, self._flag, self._steps,
+                              self.growth_factor, self.backoff_factor, self.growth_interval)
+        return None
+
+    def _clipped_step(self, work):
+        n = sum(t.n_blocks for _, _, t in work)
+        if self._partials is None or self._partials.numel() != n:
+            # allocated when the tables are (re)built — the eager warm-up steps — so that a captured step reads a fixed address
+            self._partials = torch.zeros(n, dtype=torch.float64, device=self._steps.device)
+        off = 0
+        for _, _, t in work:                                   # 1. the non-finite check and the sum of squares, one pass
+            off += ops.grads_sumsq_check(t, self._partials[off:off + t.n_blocks], self._flag)
+        # 2. the norm of the un-scaled gradients and the coefficient (one workgroup)
+        ops.grad_norm_clip_coef(self._partials, self.loss_scale, self.max_grad_norm, self.grad_norm, self.clip_coef)
+        for gi, g, t in work:                                  # 3. the update on grad / S * coef, or nothing
+            ops.adam_amsgrad_step(t, self._lr_tensor(gi, g), self._steps[gi], self.loss_scale, self._flag, g['betas'][0],
+                                  g['betas'][1], g['eps'], g['weight_decay'], clip_coef=self.clip_coef)
+        # 4. step counters, scale, tracker, skipped count; clears the flag
         ops.loss_scale_update(self.loss_scale, self.growth_tracker, self.skipped_steps, self._flag, self._steps,
                               self.growth_factor, self.backoff_factor, self.growth_interval)
         return None

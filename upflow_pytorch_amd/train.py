@@ -45,7 +45,7 @@ class Trainer():
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-4, scheduler_gamma=1.0, device=None, distributed=None, graph=False,
                  batch_check='collective', fused_adam=None, loss_scale=None, growth_interval=2000, growth_factor=2.0,
-                 backoff_factor=0.5):
+                 backoff_factor=0.5, max_grad_norm=None):
         """fused_adam: the optimizer step as ONE multi-tensor kernel (torch.optim.Adam(fused=True): the same update formulas —
         Adam + amsgrad + L2 weight decay, scripts/simple_train.py:119-130 — in one pass over the 80 parameters instead of the
         15 `foreach` launches, 0.23 ms of a 11.8 ms step); default: on a GPU.
@@ -61,10 +61,23 @@ class Trainer():
         or, after growth_interval clean steps, multiplied by growth_factor; all of it kernels on the stream, inside the captured
         step (torch.amp.GradScaler's defaults and state machine, without its host synchronisation); a positive power of two —
         that fixed S, non-finite steps still skipped and counted.  The stats gain 'loss_scale' and 'skipped_steps' (the values
-        AFTER the step); `loss` stays the unscaled loss.  GPU only."""
+        AFTER the step); `loss` stays the unscaled loss.  GPU only.
+        max_grad_norm: None (default) — nothing is measured or clipped; a positive float — the global L2 norm of the un-scaled
+        gradients is bounded inside the step as torch.nn.utils.clip_grad_norm_ bounds it (optim.NativeAdam(max_grad_norm=...): the
+        coefficient is folded into Adam's read, p.grad keeps the unclipped, still scaled values); math.inf — the norm is measured
+        only.  The optimizer is then an optim.NativeAdam with the given loss_scale, or with a FIXED scale of 1.0 when loss_scale
+        is None: a step with a non-finite gradient is then skipped and counted (optimizer.skipped_steps) instead of poisoning
+        the weights as torch's Adam would.  The stats gain 'grad_norm' (the pre-clip norm of that step's un-scaled gradients;
+        non-finite exactly on a skipped step); 'loss_scale' and 'skipped_steps' appear when loss_scale is set, as before.
+        GPU only."""
         from . import optim as _optim
         from ._lib import UpflowHipError
         self._loss_scaling = loss_scale is not None
+        self.max_grad_norm = _optim.parse_max_grad_norm(max_grad_norm)      # ValueError for <= 0, NaN, a non-number
+        self._native_step = self._loss_scaling or self.max_grad_norm is not None
+        if self.max_grad_norm is not None and (device is None or torch.device(device).type != 'cuda'):
+            raise UpflowHipError('max_grad_norm=%r needs a GPU (device=%r): the clipped step is native kernels only, there is no '
+                                 'CPU path' % (max_grad_norm, device))
         if self._loss_scaling:
             _optim.parse_loss_scale(loss_scale)              # ValueError for anything but 'dynamic' / a positive power of two
             if device is None or torch.device(device).type != 'cuda':
@@ -106,7 +119,11 @@ class Trainer():
         if self._loss_scaling:
             self.optimizer = _optim.NativeAdam([p for p in self.net.parameters() if p.requires_grad], lr=lr_arg, amsgrad=True,
                                                weight_decay=weight_decay, loss_scale=loss_scale, growth_interval=growth_interval,
-                                               growth_factor=growth_factor, backoff_factor=backoff_factor)
+                                               growth_factor=growth_factor, backoff_factor=backoff_factor,
+                                               max_grad_norm=self.max_grad_norm)
+        elif self._native_step:                              # (a bound on the norm alone: a fixed scale of 1)
+            self.optimizer = _optim.NativeAdam([p for p in self.net.parameters() if p.requires_grad], lr=lr_arg, amsgrad=True,
+                                               weight_decay=weight_decay, loss_scale=1.0, max_grad_norm=self.max_grad_norm)
         else:
             self.optimizer = torch.optim.Adam([p for p in self.net.parameters() if p.requires_grad], lr=lr_arg, amsgrad=True,
                                               weight_decay=weight_decay, capturable=self.use_graph, fused=self.fused_adam)
@@ -131,11 +148,15 @@ class Trainer():
         (`tr.optimizer = torch.optim.Adam(..., fused=True)`) — gets the hook, and the replay path's parameter list follows it
         (a replaced fused optimizer had neither, and the step kept multiplying by the step-0 packed weights)."""
         from . import ops as _ops
-        if getattr(self, '_loss_scaling', False):
-            # the scale, the overflow flag and the skipped step live in the optimizer: any other one would be fed SCALED gradients
+        if getattr(self, '_native_step', False):
+            # the scale, the overflow flag, the skipped step and the norm live in the optimizer: any other one would be fed SCALED
+            # gradients, or leave 'grad_norm' without a source
             from .optim import NativeAdam
             if not isinstance(opt, NativeAdam):
-                raise TypeError('a Trainer with loss_scale set takes an optim.NativeAdam only, got %s' % type(opt).__name__)
+                raise TypeError('a Trainer with %s set takes an optim.NativeAdam only, got %s'
+                                % ('loss_scale' if self._loss_scaling else 'max_grad_norm', type(opt).__name__))
+            if self.max_grad_norm is not None and opt.max_grad_norm is None:
+                raise TypeError('a Trainer with max_grad_norm set takes an optim.NativeAdam(max_grad_norm=...) only')
         self._optimizer = opt
         _ops.register_version_hook(opt)
         self._params_flat = [p for g in opt.param_groups for p in g['params']]
@@ -189,7 +210,9 @@ class Trainer():
         if self._loss_scaling:
             # S seeds the backward pass (a device scalar: no multiply node, and the captured step reads its current value).  Under
             # DDP the all-reduce averages the SCALED gradients; a NaN / inf on any rank is non-finite on every rank after the
-            # reduction, so each rank's check takes the same decision — skip, back off — with no extra collective.
+            # reduction, so each rank's check takes the same decision — skip, back off — with no extra collective.  The same
+            # argument covers max_grad_norm: after the bucket all-reduce every rank holds the same gradients, so the same norm
+            # and the same clip coefficient.
             loss.backward(gradient=self.optimizer.loss_scale)
         else:
             loss.backward()                  # DDP overlaps the gradient all-reduce with the rest of backward
@@ -207,6 +230,9 @@ class Trainer():
         if self._loss_scaling:               # (the same on every rank: appended after the averaging)
             self._names = self._names + ['loss_scale', 'skipped_steps']
             stats = torch.cat([stats, self.optimizer.loss_scale.reshape(1), self.optimizer.skipped_steps.reshape(1).float()])
+        if self.max_grad_norm is not None:   # (the pre-clip norm of this step's un-scaled gradients; the same on every rank)
+            self._names = self._names + ['grad_norm']
+            stats = torch.cat([stats, self.optimizer.grad_norm.reshape(1)])
         return stats
 
     def _capture(self, batch):
