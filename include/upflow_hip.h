@@ -779,6 +779,35 @@ int upf_frames_u8_stack16(const unsigned char* src1, const unsigned char* src2, 
                           void* xd, int xd_dtype, long long xd_pitch, long long xd_batch_stride,
                           int B, int H, int W, double mean0, double mean1, double mean2, double stddev, void* stream);
 
+/* ---- KITTI scoring from the uint16 ground truth --------------------------------------------------------------------------------
+ * The evaluation metrics of the reference (dataset/kitti_dataset.py:379-499: flow_error_avg three times, outlier_pct once) of one
+ * batch as ONE result row, from the prediction and the payload of the two KITTI flow PNGs as the files hold it:
+ *   pred            fp32   [B,2,H,W] contiguous
+ *   gt_occ, gt_noc  uint16 [B,H,W,3] contiguous: R = u*64 + 2^15, G = v*64 + 2^15, B = valid
+ * Per pixel, every step ONE fp32 operation rounded to nearest (no contraction), sqrt the CORRECTLY ROUNDED fp32 square root:
+ *   gu = (float)((int)R - 32768) * 0.015625f, gv likewise   (exact: the host path's float64 decode, rounded to fp32)
+ *   m_occ = (float)(B_occ & 255), m_noc = (float)(B_noc & 255)                     (the host path's np.uint8() wraps)
+ *   du = gu - pu, dv = gv - pv        (from gt_occ for the occ / F1 / occluded-only terms, from gt_noc for the noc term)
+ *   e   = sqrt(du*du + dv*dv)
+ *   thr = max(3.0f, sqrt(gu*gu + gv*gv) * 0.05f)              (gt_occ; 0.05 as fp32)
+ *   d_occ = e_occ * m_occ;   outlier = d_occ > thr (never for a NaN);   w_oo = m_occ - m_noc  (negative where noc is not in occ)
+ * Sums over the B*H*W pixels, float terms in double, masks and counts as exact integers:
+ *   S_occ = sum d_occ, N_occ = sum m_occ, C_out = sum outlier, S_noc = sum e_noc*m_noc, N_noc = sum m_noc,
+ *   S_oo = sum e_occ*w_oo, N_oo = sum w_oo
+ *   row[0..12) = { S_occ/(N_occ+1e-6), C_out/N_occ*100, S_noc/(N_noc+1e-6), S_oo/(N_oo+1e-6),
+ *                  S_occ, N_occ, C_out, S_noc, N_noc, S_oo, N_oo, (double)B }
+ * (an empty mask: F1 = 0/0 = NaN and EPE = 0, as the reference; a NaN in pred makes the S sums it enters NaN.)  Why the square
+ * root is pinned: the F1 count is made of `d_occ > thr` comparisons, and a 1-ulp square root (the native instruction, or torch's
+ * vectorised CPU sqrt) flips the ones whose error sits on the threshold.
+ * Two launches on `stream`: partial sums per workgroup into `workspace` (upf_kitti_score_workspace_bytes(B,H,W) bytes through
+ * *bytes, 8-byte aligned), then one workgroup adds them in a fixed order and writes row — 12 doubles of DEVICE memory, e.g.
+ * table + 12 * index; nothing else is written.  No atomics and no workgroup waits for another: the row is bit-reproducible run to
+ * run.  UPF_EINVAL: null pointers, non-positive sizes; UPF_EUNSUPPORTED: 2^31 pixels or more; UPF_EALIGN: pred / workspace / row
+ * not 8-byte, gt_occ / gt_noc not 4-byte aligned. */
+int upf_kitti_score_workspace_bytes(int B, int H, int W, long long* bytes);
+int upf_kitti_score(const float* pred, const unsigned short* gt_occ, const unsigned short* gt_noc, void* workspace,
+                    double* row, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

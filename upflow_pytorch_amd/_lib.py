@@ -114,8 +114,9 @@ SIGNATURES = {
     'upf_loss_scale_update': [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp],
     'upf_frames_u8_assemble': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp],
     'upf_frames_u8_stack16': [_vp, _vp, _vp, _vp, _i, _ll, _ll, _vp, _i, _ll, _ll, _i, _i, _i, _d, _d, _d, _d, _vp],
+    'upf_kitti_score_workspace_bytes': [_i, _i, _i, _c.POINTER(_ll)],
+    'upf_kitti_score': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
-
 
 
 class WgradLevel(_c.Structure):

@@ -178,14 +178,27 @@ class kitti_flow:
         return data
 
     class kitti_train():
-        def __init__(self, name, root=None, u8=False):
+        def __init__(self, name, root=None, u8=False, gt_u16=False):
             """u8=True: im1 / im2 come back as the decoded uint8 [H,W,3] frames — Test_model.eval_forward normalises them on the
-            device (ops.frames_from_u8), bit for bit what the default item holds; flows and masks are unchanged."""
+            device (ops.frames_from_u8), bit for bit what the default item holds; flows and masks are unchanged.
+            gt_u16=True: a training-split item is (im1, im2, gt_occ, gt_noc), the last two the payload of the two flow PNGs as
+            torch.uint16 [H,W,3] (R = u*64 + 2^15, G = v*64 + 2^15, B = valid) — undecoded work for ops.kitti_score
+            (Evaluation_bench(device_score=True)); the frames follow `u8`."""
             assert name in ['2012_train', '2015_train', '2012_test', '2015_test']
             self.file_names = kitti_flow.get_file_names(root)[name]
             self.normalize = True
             self.name = name
             self.u8 = bool(u8)
+            self.gt_u16 = bool(gt_u16)
+
+        @staticmethod
+        def read_gt_u16(fpath):
+            """KITTI flow PNG -> torch.uint16 [H,W,3]; a fourth channel is dropped, anything but 16-bit RGB raises as
+            flow_io.read_kitti_png_flow does."""
+            gt = flow_io.read_png(fpath)
+            if gt.dtype != np.uint16 or gt.shape[2] < 3:
+                raise ValueError('%s: a 16-bit RGB PNG expected, got %s %s' % (fpath, gt.dtype, gt.shape))
+            return torch.from_numpy(np.ascontiguousarray(gt[:, :, :3]))
 
         def __len__(self):
             return len(self.file_names)
@@ -196,6 +209,8 @@ class kitti_flow:
                 frames = [torch.from_numpy(np.ascontiguousarray(flow_io.read_image(d[k]))) for k in ('im1', 'im2')]
                 if self.name.endswith('_test'):
                     return frames[0], frames[1], os.path.basename(d['im1']).replace('.png', '')
+                if self.gt_u16:
+                    return frames[0], frames[1], self.read_gt_u16(d['flow_occ']), self.read_gt_u16(d['flow_noc'])
                 occ, occmask = img_func.read_png_flow(d['flow_occ'])
                 noc, nocmask = img_func.read_png_flow(d['flow_noc'])
                 return tuple(frames + img_func.np_2_tensor(occ, occmask, noc, nocmask))
@@ -204,6 +219,8 @@ class kitti_flow:
             if self.name.endswith('_test'):
                 im1, im2 = img_func.np_2_tensor(im1, im2)
                 return im1, im2, os.path.basename(d['im1']).replace('.png', '')
+            if self.gt_u16:
+                return tuple(img_func.np_2_tensor(im1, im2)) + (self.read_gt_u16(d['flow_occ']), self.read_gt_u16(d['flow_noc']))
             occ, occmask = img_func.read_png_flow(d['flow_occ'])
             noc, nocmask = img_func.read_png_flow(d['flow_noc'])
             return tuple(img_func.np_2_tensor(im1, im2, occ, occmask, noc, nocmask))
@@ -211,12 +228,21 @@ class kitti_flow:
     class Evaluation_bench():
         """`bench(test_model)` -> (all EPE, F1 %, non-occluded EPE, occluded-only EPE), dataset/kitti_dataset.py:379-451."""
 
-        def __init__(self, name, if_gpu=True, batch_size=1, root=None, dataset=None):
+        def __init__(self, name, if_gpu=True, batch_size=1, root=None, dataset=None, device_score=False, save_lag=8):
+            """device_score=True (not in the reference): items are (im1, im2, gt_occ, gt_noc) with the ground truth as the uint16
+            [H,W,3] PNG payload (kitti_train(gt_u16=True), or an in-memory `dataset` of such tuples); every batch is scored by ONE
+            ops.kitti_score call into a device table whose rows reach the host by asynchronous copies, and eval_save_result is
+            called in order but late: as soon as a batch's row has arrived, at the latest when more than `save_lag` batches wait.
+            There is no CPU form of it: if_gpu=False raises."""
             assert name in ['2012_train', '2015_train', '2012_test', '2015_test']
+            if device_score and not if_gpu:
+                raise ValueError('Evaluation_bench: device_score=True scores on the GPU (ops.kitti_score); there is no CPU fallback')
             self.name = name
             self.batch_size = batch_size
             self.if_gpu = if_gpu
-            self.dataset = dataset if dataset is not None else kitti_flow.kitti_train(name=name, root=root)
+            self.device_score = bool(device_score)
+            self.save_lag = max(int(save_lag), 0)
+            self.dataset = dataset if dataset is not None else kitti_flow.kitti_train(name=name, root=root, gt_u16=self.device_score)
 
         def _dev(self, *ts):
             return [t.cuda(non_blocking=True) if self.if_gpu else t for t in ts]
@@ -251,6 +277,9 @@ class kitti_flow:
                 save_name = 'all_%.2f f1_%.1f noc_%.2f occ_%.2f__%d' % (meters[0].val, meters[1].val, meters[2].val, meters[3].val, index[0])
                 test_model.eval_save_result(save_name, predflow, occmask=occmask)
 
+            if self.device_score:
+                score, finish = self._device_scorer(test_model)
+
             stream_fn = getattr(test_model, 'eval_forward_stream', None)
             if stream_fn is not None and getattr(test_model, 'pipe', None) is not None:
                 # several pairs in flight (not in the reference, whose loop is strictly one pair at a time): the forward of the next
@@ -267,7 +296,52 @@ class kitti_flow:
             else:
                 for batch in batches():
                     score(batch, test_model.eval_forward(*batch))
+            if self.device_score:
+                return finish()
             return meters[0].avg, meters[1].avg, meters[2].avg, meters[3].avg
+
+        def _device_scorer(self, test_model):
+            """-> (score(batch, predflow), finish() -> the four averages) of the device_score path.  score enqueues, on the current
+            stream behind the prediction: ops.kitti_score into row `index` of a device table, the copy of that row into a pinned
+            host table, an event.  Nothing in it reads a device value; the hook calls wait in `pending`."""
+            from collections import deque
+            from .. import ops
+            rows = max(len(self.dataset), 1)
+            table = torch.zeros((rows, ops.SCORE_ROW), dtype=torch.float64, device='cuda')
+            host = torch.zeros((rows, ops.SCORE_ROW), dtype=torch.float64).pin_memory()
+            pending = deque()                                             # (index, event, predflow, occmask), oldest first
+            count = [0]
+
+            def deliver(keep):
+                # in order: everything whose row has arrived, and the oldest ones (waited for) while more than `keep` wait
+                while pending and (len(pending) > keep or pending[0][1].query()):
+                    index, ev, predflow, occmask = pending.popleft()
+                    ev.synchronize()
+                    save_name = 'all_%.2f f1_%.1f noc_%.2f occ_%.2f__%d' % (tuple(host[index, :4].tolist()) + (index,))
+                    test_model.eval_save_result(save_name, predflow, occmask=occmask)
+
+            def score(batch, predflow):
+                index = count[0]
+                count[0] += 1
+                gt_occ, gt_noc = batch[2], batch[3]
+                # (a 16-bit prediction is promoted as `occ - predflow` promotes it on the default path)
+                ops.kitti_score(predflow.float().contiguous(), gt_occ, gt_noc, out=table[index])
+                host[index].copy_(table[index], non_blocking=True)
+                occmask = (gt_occ[..., 2].to(torch.int32) & 255).to(torch.float32).unsqueeze(1)     # np.uint8() of the host path
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append((index, ev, predflow, occmask))
+                deliver(self.save_lag)
+
+            def finish():
+                deliver(-1)
+                meters = [tools.AverageMeter() for _ in range(4)]
+                for row in host[:count[0]].tolist():
+                    for m, v in zip(meters, row[:4]):
+                        m.update(val=v, num=int(row[ops.SCORE_ROW - 1]))
+                return meters[0].avg, meters[1].avg, meters[2].avg, meters[3].avg
+
+            return score, finish
 
         @classmethod
         def flow_error_avg(cls, flow_1, flow_2, mask):

@@ -2712,3 +2712,35 @@ def stack_frames_u8(frames1_u8, frames2_u8, dtype, dec_dtype=None, pitched=True,
                 _lib.ptr(X), _lib.dtype_code(X), px, X.stride(0), _lib.ptr(Xd), _lib.dtype_code(Xd) if dual else 0, pd, Xd.stride(0) if dual else 0,
                 B, H, W, *consts)
     return (X, Xd) if dual else X
+
+
+# ---- KITTI scoring from the uint16 ground truth (csrc/score.hip) ------------------------------------------------------------------
+SCORE_ROW = 12          # doubles per result row: EPE all, F1 %, EPE noc, EPE occluded-only, the seven sums, the batch size
+
+
+def kitti_score(pred, gt_occ_u16, gt_noc_u16, out=None):
+    """The four KITTI numbers of one batch (Evaluation_bench's flow_error_avg x 3 and outlier_pct) and the sums behind them as ONE
+    float64 [12] device row (include/upflow_hip.h, upf_kitti_score), from pred fp32 [B,2,H,W] and the payload of the two flow
+    PNGs, uint16 [B,H,W,3] as flow_io.read_png returns it: two launches on the current stream, no host synchronisation,
+    bit-reproducible.  out: a float64 [12] device tensor to write, e.g. row `index` of a [N,12] table; else a new tensor."""
+    who = 'kitti_score'
+    for name, t, dt in (('pred', pred, torch.float32), ('gt_occ_u16', gt_occ_u16, torch.uint16), ('gt_noc_u16', gt_noc_u16, torch.uint16)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 4:
+            raise UpflowHipError('%s: `%s` must be a 4-d %s tensor, got %s' % (who, name, dt, (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t)))
+    B, C, H, W = pred.shape
+    if C != 2 or min(B, H, W) < 1:
+        raise UpflowHipError('%s: pred [B,2,H,W] expected, got %s' % (who, tuple(pred.shape)))
+    for name, t in (('gt_occ_u16', gt_occ_u16), ('gt_noc_u16', gt_noc_u16)):
+        if tuple(t.shape) != (B, H, W, 3):
+            raise UpflowHipError('%s: `%s` must be [%d,%d,%d,3] (R, G, B of the KITTI flow PNG), got %s' % (who, name, B, H, W, tuple(t.shape)))
+    dev = _lib.check_gpu(pred, gt_occ_u16, gt_noc_u16, out)
+    if out is None:
+        out = torch.empty((SCORE_ROW,), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (SCORE_ROW,):
+        raise UpflowHipError('%s: `out` must be a float64 [%d] tensor, got %s %s' % (who, SCORE_ROW, tuple(out.shape), out.dtype))
+    import ctypes
+    nbytes = ctypes.c_longlong(0)
+    _lib.call('upf_kitti_score_workspace_bytes', B, H, W, ctypes.byref(nbytes))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    _lib.launch(dev, 'upf_kitti_score', _lib.ptr(pred), _lib.ptr(gt_occ_u16), _lib.ptr(gt_noc_u16), _lib.ptr(ws), _lib.ptr(out), B, H, W)
+    return out

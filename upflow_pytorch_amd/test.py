@@ -79,10 +79,13 @@ class Test_model(tools.abs_test_model):
         print(save_name)
 
 
-def kitti_2015_test(pretrain_path='./scripts/upflow_kitti2015.pth', dtype=torch.float32, root=None):
+def kitti_2015_test(pretrain_path='./scripts/upflow_kitti2015.pth', dtype=torch.float32, root=None, device_score=False):
+    """device_score=True (not in the reference): undecoded items — uint8 frames, uint16 ground truth — and the metrics of every
+    pair from one ops.kitti_score call on the device (Evaluation_bench(device_score=True)); the same four numbers."""
     from .dataset.kitti_dataset import kitti_flow
     # note that eval batch size should be 1 for KITTI 2012 and KITTI 2015 (image size may be different for different sequence)
-    bench = kitti_flow.Evaluation_bench(name='2015_train', if_gpu=True, batch_size=1, root=root)
+    dataset = kitti_flow.kitti_train(name='2015_train', root=root, u8=True, gt_u16=True) if device_score else None
+    bench = kitti_flow.Evaluation_bench(name='2015_train', if_gpu=True, batch_size=1, root=root, dataset=dataset, device_score=device_score)
     testmodel = Test_model(pretrain_path=pretrain_path, dtype=dtype)
     epe_all, f1, epe_noc, epe_occ = bench(testmodel)
     print('EPE All = %.2f, F1 = %.2f, EPE Noc = %.2f, EPE Occ = %.2f' % (epe_all, f1, epe_noc, epe_occ))
