@@ -808,6 +808,35 @@ int upf_kitti_score_workspace_bytes(int B, int H, int W, long long* bytes);
 int upf_kitti_score(const float* pred, const unsigned short* gt_occ, const unsigned short* gt_noc, void* workspace,
                     double* row, int B, int H, int W, void* stream);
 
+/* ---- evaluation results: KITTI PNG samples, Middlebury colours, .flo body ---------------------------------------------------------
+ * What the reference's runner saves per pair (utils/tools.py:1342-1480 flow_to_image, :1482-1525 write_flow_png, :1556-1632
+ * write_flo), as the PAYLOADS of the three files, from the prediction on the device:
+ *   pred   fp32   [B,2,H,W] contiguous;   valid  fp32 [B,1,H,W] contiguous or NULL (= 1 everywhere)
+ *   kitti  uint16 [B,H,W,3]   R, G = clip(double(x) * 64.0 + 32768.0, 0, 65535) truncated (the bits of flow_io.write_kitti_png_file's
+ *                             encode; +-inf clamp), B = valid truncated to uint16 (saturating; NaN -> 0).  A NaN component of
+ *                             the flow makes the pixel (0, 0, 0): the host's cast of a NaN is undefined, this is defined.
+ *   rgb    uint8  [B,H,W,3]   flow_to_image as it evaluates for a float32 frame (below)
+ *   flo    fp32   [B,H,W,2]   the two planes interleaved, bit for bit
+ * Each output may be NULL (not wanted); all three NULL is UPF_EINVAL.
+ * rgb.  In fp32, each step rounded on its own, sqrt correctly rounded: a pixel with |u| or |v| > 1e7 (unknown) or with a NaN
+ * component is BLACK and counts as (0,0); maxrad = max over the ITEM of sqrt(u*u + v*v).  (The reference lets a NaN turn the whole
+ * frame's scale into -1; here it is one black pixel.)  max_rad > 0 replaces maxrad for every item; max_rad <= 0 (or NaN) = per item.
+ * Then in float64: d = double(maxrad) + 2^-52, u = double(u)/d, v likewise, rad = sqrt(u*u + v*v),
+ *   fk = (atan2(-v,-u)/pi + 1)/2 * 54 + 1, k0 = floor(fk), k1 = k0 + 1 (56 -> 1), f = fk - k0,
+ *   c = (1-f) * wheel[k0-1]/255 + f * wheel[k1-1]/255 per channel (the 55-entry Middlebury wheel: segments of 15, 6, 4, 11, 13, 6
+ *   entries, ramps floor(255*i/n)),  c = rad <= 1 ? 1 - rad*(1-c) : c*0.75,  stored floor(255*c).
+ * Every operation but atan2 is IEEE-exact, so a value differs from the host's only where the angle's last bit moves a floor.
+ * Launches on `stream`: ONE when no per-item maximum is needed (rgb NULL, or max_rad > 0) — the workspace is then not touched and
+ * may be NULL; else two: per-workgroup partial maxima into `workspace` (upf_flow_export_workspace_bytes(B,H,W) bytes through
+ * *bytes), then every workgroup folds its item's and renders.  No atomics, no workgroup waits for another; nothing but the
+ * requested outputs and the workspace is written; same bits run to run.  Four consecutive pixels per lane, moved with the widest
+ * access the addresses allow (any H*W; 16-byte aligned bases and H*W % 4 == 0 give the widest).
+ * UPF_EINVAL: null pred, no output, a needed workspace missing, non-positive sizes; UPF_EUNSUPPORTED: 2^31 pixels or more;
+ * UPF_EALIGN: pred / valid / flo / workspace not 4-byte, kitti not 2-byte aligned. */
+int upf_flow_export_workspace_bytes(int B, int H, int W, long long* bytes);
+int upf_flow_export(const float* pred, const float* valid, unsigned short* kitti, unsigned char* rgb, float* flo,
+                    float max_rad, void* workspace, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

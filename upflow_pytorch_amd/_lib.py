@@ -116,6 +116,8 @@ SIGNATURES = {
     'upf_frames_u8_stack16': [_vp, _vp, _vp, _vp, _i, _ll, _ll, _vp, _i, _ll, _ll, _i, _i, _i, _d, _d, _d, _d, _vp],
     'upf_kitti_score_workspace_bytes': [_i, _i, _i, _c.POINTER(_ll)],
     'upf_kitti_score': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    'upf_flow_export_workspace_bytes': [_i, _i, _i, _c.POINTER(_ll)],
+    'upf_flow_export': [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp],
 }
 
 

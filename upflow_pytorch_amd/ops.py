@@ -2744,3 +2744,65 @@ def kitti_score(pred, gt_occ_u16, gt_noc_u16, out=None):
     ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
     _lib.launch(dev, 'upf_kitti_score', _lib.ptr(pred), _lib.ptr(gt_occ_u16), _lib.ptr(gt_noc_u16), _lib.ptr(ws), _lib.ptr(out), B, H, W)
     return out
+
+
+# ---- evaluation results: KITTI PNG samples, Middlebury colours, .flo body (csrc/export.hip) ---------------------------------------
+_EXPORT_OUT = {'kitti': (torch.uint16, 3), 'color': (torch.uint8, 3), 'flo': (torch.float32, 2)}      # name -> dtype, last dim
+_export_ws = {}                                                                                        # (device, stream, B, H, W) -> uint8 tensor
+
+
+def flow_export_workspace(device, B, H, W):
+    """The cached workspace ops.flow_export uses for [B,2,H,W] predictions on `device`: one per device and shape — and per
+    current stream, since the calls of one stream use it one after the other and those of two streams would not."""
+    import ctypes
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, B, H, W)
+    ws = _export_ws.get(key)
+    if ws is None:
+        nbytes = ctypes.c_longlong(0)
+        _lib.call('upf_flow_export_workspace_bytes', B, H, W, ctypes.byref(nbytes))
+        ws = _export_ws[key] = torch.empty((nbytes.value,), dtype=torch.uint8, device=device)
+    return ws
+
+
+def flow_export(pred, valid=None, kitti=False, color=False, flo=False, max_rad=None, out=None):
+    """The payloads of the files an evaluation run saves, from pred fp32 [B,2,H,W] on the device (include/upflow_hip.h,
+    upf_flow_export) -> dict of device tensors, one per requested output:
+        'kitti'  uint16 [B,H,W,3]   the samples of the KITTI flow PNG (flow_io.write_kitti_png_u16 writes them); B channel = valid
+        'color'  uint8  [B,H,W,3]   tools.flow_to_image of every item
+        'flo'    fp32   [B,H,W,2]   the body of a .flo file (flow_io.write_flo_payload)
+    valid: fp32 [B,1,H,W] or None (1 everywhere).  max_rad: the colour scale in px for every item; None / <= 0: each item's own
+    largest radius, as the reference (one more launch).  out: dict of preallocated contiguous tensors to write (slices of larger
+    tensors included); its keys count as requested.  One or two launches on the current stream, no host synchronisation."""
+    who = 'flow_export'
+    if not torch.is_tensor(pred) or pred.dtype != torch.float32 or pred.dim() != 4:
+        raise UpflowHipError('%s: `pred` must be a 4-d float32 tensor, got %s' % (who, (tuple(pred.shape), pred.dtype) if torch.is_tensor(pred) else type(pred)))
+    B, C, H, W = pred.shape
+    if C != 2 or min(B, H, W) < 1:
+        raise UpflowHipError('%s: pred [B,2,H,W] expected, got %s' % (who, tuple(pred.shape)))
+    if valid is not None and (not torch.is_tensor(valid) or valid.dtype != torch.float32 or tuple(valid.shape) != (B, 1, H, W)):
+        raise UpflowHipError('%s: `valid` must be a float32 [%d,1,%d,%d] tensor, got %s' % (who, B, H, W, (tuple(valid.shape), valid.dtype) if torch.is_tensor(valid) else type(valid)))
+    out = dict(out) if out else {}
+    unknown = set(out) - set(_EXPORT_OUT)
+    if unknown:
+        raise UpflowHipError('%s: `out` has unknown keys %s (kitti, color, flo)' % (who, sorted(unknown)))
+    wanted = [name for name, flag in (('kitti', kitti), ('color', color), ('flo', flo)) if flag or out.get(name) is not None]
+    if not wanted:
+        raise UpflowHipError('%s: no output requested (kitti, color, flo)' % who)
+    dev = _lib.check_gpu(pred, valid, *[out[name] for name in wanted if torch.is_tensor(out.get(name))])
+    res = {}
+    for name in wanted:
+        dt, last = _EXPORT_OUT[name]
+        t = out.get(name)
+        if t is None:
+            t = torch.empty((B, H, W, last), dtype=dt, device=dev)
+        elif not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (B, H, W, last):
+            raise UpflowHipError('%s: out[%r] must be a %s [%d,%d,%d,%d] tensor, got %s' % (who, name, dt, B, H, W, last, (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t)))
+        res[name] = t
+    max_rad = 0.0 if max_rad is None else float(max_rad)
+    ws = flow_export_workspace(dev, B, H, W) if 'color' in res and not max_rad > 0.0 else None
+    _lib.launch(dev, 'upf_flow_export', _lib.ptr(pred), _lib.ptr(valid), _lib.ptr(res.get('kitti')), _lib.ptr(res.get('color')),
+                _lib.ptr(res.get('flo')), max_rad, _lib.ptr(ws), B, H, W)
+    return res

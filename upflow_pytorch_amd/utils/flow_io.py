@@ -50,6 +50,18 @@ def read_flo(filename):
     return data.reshape(h, w, 2)
 
 
+def write_flo_payload(payload, filename):
+    """payload: float32 [H,W,2], (u,v) interleaved — the body of the file as ops.flow_export(flo=True) produces it -> .flo; the
+    bytes write_flo writes for the same flow, without a conversion."""
+    payload = np.asarray(payload)
+    if payload.dtype != np.float32 or payload.ndim != 3 or payload.shape[2] != 2:
+        raise ValueError('write_flo_payload: float32 [H,W,2] expected, got %s %s' % (payload.dtype, payload.shape))
+    h, w = payload.shape[:2]
+    with open(filename, 'wb') as f:
+        f.write(struct.pack('<fii', FLO_MAGIC, w, h))
+        f.write(np.ascontiguousarray(payload).data)
+
+
 write_flow, read_flow = write_flo, read_flo
 
 
@@ -181,6 +193,15 @@ def write_kitti_png_file(flow_fn, flow_data, mask_data=None):
     valid = np.ones((h, w), dtype=np.uint16) if mask_data is None else np.asarray(mask_data).reshape(h, w).astype(np.uint16)
     enc = np.clip(flow_data * 64.0 + 2 ** 15, 0.0, 65535.0).astype(np.uint16)     # (write_flow_png clips; so do we)
     write_png(flow_fn, np.stack([enc[:, :, 0], enc[:, :, 1], valid], axis=-1))
+
+
+def write_kitti_png_u16(flow_fn, encoded):
+    """encoded: uint16 [H,W,3], R = u*64 + 2^15, G = v*64 + 2^15, B = valid, already encoded — by ops.flow_export(kitti=True),
+    or read from a KITTI file — -> the file write_kitti_png_file writes for the flow and mask it stands for."""
+    encoded = np.asarray(encoded)
+    if encoded.dtype != np.uint16 or encoded.ndim != 3 or encoded.shape[2] != 3:
+        raise ValueError('write_kitti_png_u16: uint16 [H,W,3] expected, got %s %s' % (encoded.dtype, encoded.shape))
+    write_png(flow_fn, encoded)
 
 
 def write_flow_png(filename, uv, v=None, mask=None):

@@ -5,7 +5,8 @@ namespace), so code written against the reference (`tools.torch_warp(x, flo)`,
 `tools.occ_check_model(...)(flow_f=..., flow_b=...)`, `tools.abstract_config`, `net.load_model(...)`)
 keeps working; the arithmetic runs in the HIP kernels of libupflow_hip.so.
 File formats (.flo, KITTI flow PNG) live in utils/flow_io.py, the KITTI readers and the evaluation bench in
-dataset/kitti_dataset.py.  Out of scope: data prefetcher, visualisation, SP_transform.
+dataset/kitti_dataset.py.  Out of scope: data prefetcher, SP_transform, visualisations other than
+flow_to_image.
 """
 import torch
 import torch.nn as nn
@@ -166,6 +167,55 @@ class tools():
     def write_flow_png(cls, filename, uv, v=None, mask=None):
         from . import flow_io
         flow_io.write_flow_png(filename, uv, v, mask)
+
+    # ---- visualisation (utils/tools.py:1342-1480); the device form is ops.flow_export(color=True) -------------------------------
+    @classmethod
+    def color_wheel(cls):
+        """The 55-entry Middlebury colour wheel, float64 [55,3]: red -> yellow -> green -> cyan -> blue -> magenta -> red in
+        segments of 15, 6, 4, 11, 13 and 6 entries, the moving channel a ramp floor(255 * i / n)."""
+        import numpy as np
+        wheel = np.zeros((55, 3))
+        at = 0
+        # (segment length, channel held at 255, channel that moves, +1 rising / -1 falling)
+        for n, held, moving, sign in ((15, 0, 1, 1), (6, 1, 0, -1), (4, 1, 2, 1), (11, 2, 1, -1), (13, 2, 0, 1), (6, 0, 2, -1)):
+            ramp = np.floor(255 * np.arange(n) / n)
+            wheel[at:at + n, held] = 255
+            wheel[at:at + n, moving] = ramp if sign > 0 else 255 - ramp
+            at += n
+        return wheel
+
+    @classmethod
+    def flow_to_image(cls, flow, display=False, max_rad=None):
+        """flow [H,W,2] -> Middlebury colour code, uint8 [H,W,3] (utils/tools.py:1342-1480; DESIGN §12 has the arithmetic).  The
+        largest radius is taken in the frame's own type (fp32 for a float32 frame), everything after it in float64, as the
+        reference evaluates.  Pixels with |u| or |v| > 1e7 are unknown: black, and (0,0) for the maximum.  Two differences: the
+        input is not modified, and a NaN pixel is black and left out of the maximum (the reference's scale becomes -1 for the whole
+        frame).  max_rad (not in the reference): a given scale in px instead of the frame's own."""
+        import numpy as np
+        flow = np.asarray(flow)
+        if not np.issubdtype(flow.dtype, np.floating):
+            flow = flow.astype(np.float64)
+        u, v = flow[:, :, 0], flow[:, :, 1]
+        with np.errstate(invalid='ignore', over='ignore'):
+            black = (np.abs(u) > 1e7) | (np.abs(v) > 1e7) | np.isnan(u) | np.isnan(v)
+            u, v = np.where(black, 0, u).astype(flow.dtype), np.where(black, 0, v).astype(flow.dtype)
+            maxrad = np.max(np.sqrt(u * u + v * v)) if max_rad is None or not max_rad > 0 else np.float32(max_rad)
+            if display:
+                print("max flow: %.4f\nflow range:\nu = %.3f .. %.3f\nv = %.3f .. %.3f" % (maxrad, u.min(), u.max(), v.min(), v.max()))
+            d = np.float64(maxrad) + np.finfo(np.float64).eps
+            u, v = u.astype(np.float64) / d, v.astype(np.float64) / d
+            rad = np.sqrt(u * u + v * v)
+            fk = (np.arctan2(-v, -u) / np.pi + 1) / 2 * 54 + 1
+            k0 = np.floor(fk).astype(np.int64)
+            k1 = np.where(k0 + 1 == 56, 1, k0 + 1)
+            f = fk - k0
+            wheel = cls.color_wheel()
+            img = np.zeros(u.shape + (3,), dtype=np.uint8)
+            for i in range(3):
+                col = (1 - f) * (wheel[k0 - 1, i] / 255) + f * (wheel[k1 - 1, i] / 255)
+                col = np.where(rad <= 1, 1 - rad * (1 - col), col * 0.75)
+                img[:, :, i] = np.where(black, 0, np.floor(255 * col)).astype(np.uint8)
+        return img
 
     class abs_test_model():
         """Evaluation protocol of utils/tools.py:157-164."""
