@@ -837,6 +837,34 @@ int upf_flow_export_workspace_bytes(int B, int H, int W, long long* bytes);
 int upf_flow_export(const float* pred, const float* valid, unsigned short* kitti, unsigned char* rgb, float* flo,
                     float max_rad, void* workspace, int B, int H, int W, void* stream);
 
+/* ---- PNG compression: filter, Huffman code, zlib stream ----------------------------------------------------------------------------
+ * From the samples of B images — img uint8 (depth 8) or uint16 (depth 16) [B,H,W,C] contiguous, C in 1..4: the `kitti` and `rgb`
+ * tensors of upf_flow_export — the complete zlib stream of each image's PNG, i.e. the body of its IDAT chunk:
+ *   out      uint8 [B,cap]  slot b holds image b's stream from its first byte; the rest of the slot is zero
+ *   lengths  int32 [B]      the stream's bytes; negative: the stream would not have fitted the slot and is not complete (cannot
+ *                           happen with the cap below; nothing is ever written beyond a slot)
+ * upf_png_encode_workspace_bytes gives the workspace's bytes and cap, the pitch of `out`: n + n/8 + 1024 rounded up to 16, where
+ * n = H * (stride + 1), stride = W * C * depth / 8, is the length of the filtered stream.
+ * The filtered stream is flow_io.write_png's: per row the filter type 2 (Up), then cur - above mod 256 over the big-endian sample
+ * bytes; the first row has above = 0.  The zlib stream: 78 01; ONE final deflate block with dynamic Huffman codes, every symbol a
+ * literal (no matches); the Adler-32, big-endian.  The block header: BFINAL 1, BTYPE 2, HLIT 0 (257 literal/length codes), HDIST 0
+ * (one distance code, length 1, never used), HCLEN 15; the code-length code gives 4 bits to the symbols 0..15 and none to 16..18;
+ * then 258 lengths of 4 bits.  The literal code, one per image, from the 256 byte counts and one end-of-block:
+ *   Huffman: the symbols with a count sorted by (count, symbol), merged with two queues (the leaves; the nodes in the order they
+ *     were made; on equal weights a leaf first); while the deepest leaf is beyond 15 bits every count becomes (count + 1) >> 1;
+ *   flat: 9 bits for the two first symbols in (count, symbol) order over all 257, 8 bits for the rest;
+ *   the flat code is taken when it costs strictly fewer bits over the true counts, so a stream is at most
+ *   2 + ceil((1106 + 9 * (n + 1)) / 8) + 4 bytes <= cap.  Canonical codes (RFC 1951 3.2.2).
+ * tests/_png_model.py states all of it in Python and gives the same bytes.  A constant image costs 1 bit per byte.
+ * Three launches on `stream` (filter + counts + Adler sums per 4096-byte chunk; the code, per image; the packing per chunk); no
+ * host synchronisation, no allocation, no workgroup waits for another; integer adds and ORs of disjoint bits only: the same bytes
+ * run to run.  Nothing but `out`, `lengths` and the workspace is written.
+ * UPF_EINVAL: null pointers, non-positive sizes, C outside 1..4, depth not 8 / 16; UPF_EUNSUPPORTED: a slot of 2^31 bytes or
+ * more; UPF_EALIGN: img not sample-aligned, out / lengths not 4-byte, workspace not 16-byte aligned. */
+int upf_png_encode_workspace_bytes(int B, int H, int W, int C, int depth, long long* bytes, long long* cap);
+int upf_png_encode(const void* img, unsigned char* out, int* lengths, void* workspace, int B, int H, int W, int C, int depth,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
 """Saving evaluation results, measured: kitti_flow.Evaluation_bench(device_score=True) over an in-memory data set of 64 synthetic
 375x1242 pairs (8 distinct items, each listed 8 times; tools/eval_score_measure.py's) with Test_model(streams=4,
-pretrain_path=None) in bf16 — one network, three models around it — three arms alternated on one box, every window PASSES full
+pretrain_path=None) in bf16 — one network, four models around it — four arms alternated on one box, every window PASSES full
 passes over the data set (host clock around a pass that ends with the files complete and a synchronise):
 
   no-save      eval_save_result does nothing: the loop alone;
   host-writer  eval_save_result copies the prediction back and calls flow_io.write_kitti_png_file on the thread that drives the
                GPU — all there was before Test_model(save_dir=...): a float64 copy, clip, cast, stack, deflate;
   save_dir     Test_model(save_dir=..., save=('kitti',), save_workers=4): ops.flow_export on the device, asynchronous copies into
-               pinned buffers, deflate and write on the worker threads; the pass ends with flush().
+               pinned buffers, deflate and write on the worker threads; the pass ends with flush();
+  png=device   the same with png='device': ops.png_encode after ops.flow_export, the zlib streams copied instead of the samples,
+               the IDAT chunk's CRC and the write on the worker threads.
 
-Both saving arms write the KITTI PNGs of the same predictions under one tmpfs directory, and the files of the last pass are
-compared byte for byte.  Then the export kernel alone: ops.flow_export back to back on one stream between two device events (so
-launch gaps are in it), against its bytes over the HBM rate.
+The saving arms write the KITTI PNGs of the same predictions under one tmpfs directory; the files of the last pass of host-writer
+and save_dir are compared byte for byte, those of png=device are decoded and compared sample for sample, and the mean file size of
+both encoders is recorded.  Then the kernels alone: ops.flow_export, and ops.png_encode on a saved prediction's samples, back to
+back on one stream between two device events (so launch gaps are in it), against their bytes over the HBM rate.
 
     python tools/eval_export_measure.py [--pairs 64] [--passes 2] [--windows 3] [--out profiles/eval_export.txt]
 """
@@ -59,6 +62,30 @@ def kernel_times(lines, iters=200):
                         nbytes / HBM_SPEC * 1e6, HBM_SPEC / 1e12))
 
 
+def png_kernel_times(lines, samples, iters=200):
+    """ops.png_encode alone on the uint16 [H,W,3] samples of one saved prediction"""
+    from upflow_pytorch_amd import ops
+    img = torch.from_numpy(samples[None]).cuda()
+    out = ops.png_encode(img)
+    for _ in range(20):
+        ops.png_encode(img, out=out)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    best = []
+    for _ in range(3):
+        a.record()
+        for _ in range(iters):
+            ops.png_encode(img, out=out)
+        b.record()
+        b.synchronize()
+        best.append(a.elapsed_time(b) / iters * 1e3)
+    n = int(out[1][0])
+    raw = samples.shape[0] * (samples.shape[1] * 6 + 1)
+    nbytes = 2 * raw + raw + raw // 8 + out[0].shape[1] + raw + n          # samples read twice; filtered written, counts, slot zeroed; filtered read, stream
+    lines.append('  png_encode, uint16 [1,%d,%d,3], three launches:       %.1f us per call (%.1f-%.1f; back to back, device events)  %.2f MB filtered -> %.2f MB stream; '
+                 '%.2f MB moved: %.2f us at %.2f TB/s measured copy rate'
+                 % (samples.shape[0], samples.shape[1], sum(best) / 3, min(best), max(best), raw / 1e6, n / 1e6, nbytes / 1e6, nbytes / HBM_MEASURED * 1e6, HBM_MEASURED / 1e12))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=64)
@@ -75,7 +102,7 @@ def main():
     from upflow_pytorch_amd.utils import flow_io
 
     tmp = tempfile.mkdtemp(prefix='upflow_export_', dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
-    dirs = {k: os.path.join(tmp, k) for k in ('host', 'dev')}
+    dirs = {k: os.path.join(tmp, k) for k in ('host', 'dev', 'devpng')}
     os.makedirs(os.path.join(dirs['host'], 'flow'))
 
     class Quiet(Test_model):
@@ -97,6 +124,8 @@ def main():
         quiet = Quiet(pretrain_path=None, dtype=torch.bfloat16, streams=4)
         host = HostWriter(pretrain_path=None, dtype=None, net=quiet.net_work, streams=4)
         device = DeviceWriter(pretrain_path=None, dtype=None, net=quiet.net_work, streams=4, save_dir=dirs['dev'], save=('kitti',), save_workers=4)
+        devpng = DeviceWriter(pretrain_path=None, dtype=None, net=quiet.net_work, streams=4, save_dir=dirs['devpng'], save=('kitti',), save_workers=4,
+                              png='device')
         new, _ = make_items(a.distinct)
         ds = [new[i % a.distinct] for i in range(a.pairs)]
         bench = kitti_flow.Evaluation_bench('2015_train', batch_size=1, dataset=ds, device_score=True)
@@ -104,7 +133,10 @@ def main():
         def saved():
             bench(device)
             device.flush()
-        arms = [('no-save', lambda: bench(quiet)), ('host-writer', lambda: bench(host)), ('save_dir', saved)]
+        def saved_png():
+            bench(devpng)
+            devpng.flush()
+        arms = [('no-save', lambda: bench(quiet)), ('host-writer', lambda: bench(host)), ('save_dir', saved), ('png=device', saved_png)]
         for _, run in arms:                                                  # captures, allocator, pinned buffers
             run()
         torch.cuda.synchronize()
@@ -118,6 +150,7 @@ def main():
                 torch.cuda.synchronize()
                 t[name].append((time.perf_counter() - t0) / (a.passes * a.pairs) * 1e3)
         device.close()
+        devpng.close()
         names = sorted(os.listdir(os.path.join(dirs['host'], 'flow')))
         same = names == sorted(os.listdir(os.path.join(dirs['dev'], 'flow'))) and len(names) == a.pairs and all(
             open(os.path.join(dirs['host'], 'flow', n), 'rb').read() == open(os.path.join(dirs['dev'], 'flow', n), 'rb').read() for n in names)
@@ -131,7 +164,18 @@ def main():
         lines.append('  saving tail (arm - no-save): host-writer %+.3f ms, save_dir %+.3f ms; save_dir / host-writer = %.3f'
                      % (mean['host-writer'] - mean['no-save'], mean['save_dir'] - mean['no-save'], mean['save_dir'] / mean['host-writer']))
         lines.append('  files of the two arms byte-identical: %s (%d files, %.0f KB each on average)' % (same, len(names), size / 1e3))
+        import numpy as np
+        pnames = sorted(os.listdir(os.path.join(dirs['devpng'], 'flow')))
+        decoded = pnames == names and all(np.array_equal(flow_io.read_png(os.path.join(dirs['devpng'], 'flow', n)), flow_io.read_png(os.path.join(dirs['dev'], 'flow', n)))
+                                          for n in names)
+        psize = sum(os.path.getsize(os.path.join(dirs['devpng'], 'flow', n)) for n in pnames) / max(len(pnames), 1)
+        lines.append('  png=device: tail %+.3f ms over no-save; png=device / save_dir = %.3f, save_dir - png=device = %.3f ms per pair (spread of the windows: save_dir %.3f, png=device %.3f)'
+                     % (mean['png=device'] - mean['no-save'], mean['png=device'] / mean['save_dir'], mean['save_dir'] - mean['png=device'],
+                        max(t['save_dir']) - min(t['save_dir']), max(t['png=device']) - min(t['png=device'])))
+        lines.append('  files of png=device decode to the samples of save_dir: %s (%d files, %.0f KB each on average; size ratio to the host writer %.3f)'
+                     % (decoded, len(pnames), psize / 1e3, psize / max(size, 1)))
         kernel_times(lines)
+        png_kernel_times(lines, flow_io.read_png(os.path.join(dirs['dev'], 'flow', names[0])))
         print('\n'.join(lines), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -139,6 +183,8 @@ def main():
                 f.write('\n'.join(lines) + '\n')
         if not same:
             raise SystemExit('eval_export_measure: the two arms wrote different files')
+        if not decoded:
+            raise SystemExit('eval_export_measure: the files of png=device do not decode to the samples of save_dir')
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 

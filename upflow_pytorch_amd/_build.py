@@ -32,6 +32,7 @@ SOURCES = [
     ('ingest.hip', ['-ffp-contract=off']),          # (float64 subtract, divide, ONE rounding: the host data path's bits)
     ('score.hip', ['-ffp-contract=off']),           # (every fp32 step of the KITTI metrics rounds on its own: an exact F1 count)
     ('export.hip', ['-ffp-contract=off']),          # (the host writer's and the reference renderer's arithmetic, step by step)
+    ('png.hip', []),                                # (integers only)
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']
 # No packed-fp32 VALU instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) anywhere in the library: on MI355X they were

@@ -2806,3 +2806,52 @@ def flow_export(pred, valid=None, kitti=False, color=False, flo=False, max_rad=N
     _lib.launch(dev, 'upf_flow_export', _lib.ptr(pred), _lib.ptr(valid), _lib.ptr(res.get('kitti')), _lib.ptr(res.get('color')),
                 _lib.ptr(res.get('flo')), max_rad, _lib.ptr(ws), B, H, W)
     return res
+
+
+# ---- PNG compression: filter, Huffman code, zlib stream (csrc/png.hip) -------------------------------------------------------------
+_PNG_DEPTH = {torch.uint8: 8, torch.uint16: 16}
+_png_ws = {}                                                  # (device, stream, B, H, W, C, depth) -> (uint8 workspace, cap)
+
+
+def png_encode_workspace(device, B, H, W, C, depth):
+    """(workspace, cap) of ops.png_encode for [B,H,W,C] images of `depth` bits on `device`: cached per device, current stream and
+    shape, as flow_export_workspace is; cap is the pitch of the stream slots (include/upflow_hip.h, upf_png_encode)."""
+    import ctypes
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, B, H, W, C, depth)
+    got = _png_ws.get(key)
+    if got is None:
+        nbytes, cap = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        _lib.call('upf_png_encode_workspace_bytes', B, H, W, C, depth, ctypes.byref(nbytes), ctypes.byref(cap))
+        got = _png_ws[key] = (torch.empty((nbytes.value,), dtype=torch.uint8, device=device), cap.value)
+    return got
+
+
+def png_encode(img, out=None):
+    """The zlib stream of every image's PNG — the body of its IDAT chunk, flow_io.write_png_stream adds the rest of the file — from
+    img uint8 / uint16 [B,H,W,C], C in 1..4, on the device: ops.flow_export's 'kitti' and 'color' as they are (include/upflow_hip.h,
+    upf_png_encode) -> (streams uint8 [B,cap], lengths int32 [B]); image b's stream is streams[b, :lengths[b]], a negative length
+    says that it did not fit (cap rules that out).  out: a contiguous uint8 [B,cap] tensor to write (a slice of a larger one
+    included), or a pair of it and an int32 [B] tensor.  Three launches on the current stream, no host synchronisation."""
+    who = 'png_encode'
+    if not torch.is_tensor(img) or img.dtype not in _PNG_DEPTH or img.dim() != 4:
+        raise UpflowHipError('%s: `img` must be a 4-d uint8 / uint16 tensor [B,H,W,C], got %s' % (who, (tuple(img.shape), img.dtype) if torch.is_tensor(img) else type(img)))
+    B, H, W, C = img.shape
+    if not 1 <= C <= 4 or min(B, H, W) < 1:
+        raise UpflowHipError('%s: img [B,H,W,C] with C in 1..4 expected, got %s' % (who, tuple(img.shape)))
+    streams, lengths = out if isinstance(out, (tuple, list)) else (out, None)
+    dev = _lib.check_gpu(img, streams, lengths)
+    depth = _PNG_DEPTH[img.dtype]
+    ws, cap = png_encode_workspace(dev, B, H, W, C, depth)
+    if streams is None:
+        streams = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    elif streams.dtype != torch.uint8 or tuple(streams.shape) != (B, cap):
+        raise UpflowHipError('%s: `out` must be a uint8 [%d,%d] tensor, got %s %s' % (who, B, cap, tuple(streams.shape), streams.dtype))
+    if lengths is None:
+        lengths = torch.empty((B,), dtype=torch.int32, device=dev)
+    elif lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+        raise UpflowHipError('%s: the lengths must be an int32 [%d] tensor, got %s %s' % (who, B, tuple(lengths.shape), lengths.dtype))
+    _lib.launch(dev, 'upf_png_encode', _lib.ptr(img), _lib.ptr(streams), _lib.ptr(lengths), _lib.ptr(ws), B, H, W, C, depth)
+    return streams, lengths

@@ -10,7 +10,12 @@ prediction to a ResultSaver, which
        and give the slot back.
 
 The caller never reads a device value.  A full ring blocks submit() until a worker is done with a slot; flush() waits for
-everything outstanding and re-raises the first worker exception; close() does the same and ends the pool."""
+everything outstanding and re-raises the first worker exception; close() does the same and ends the pool.
+
+png='device'  moves the compression of the two PNG kinds in front of the copy: step 1 goes on with ops.png_encode on the
+`kitti` / `color` payloads, step 2 copies the zlib streams' slots and their lengths instead of the samples, and a worker is left
+with the IDAT chunk's CRC and the write (flow_io.write_png_stream).  The files decode to the same samples; their bytes differ from
+the host writer's, which is why it is opt-in."""
 import os
 import queue
 import threading
@@ -41,10 +46,13 @@ class _Slot(object):
 
 
 class ResultSaver(object):
-    def __init__(self, save_dir, save=('kitti',), workers=4, max_rad=None, slots=None):
+    def __init__(self, save_dir, save=('kitti',), workers=4, max_rad=None, slots=None, png='host'):
         save = (save,) if isinstance(save, str) else tuple(save)
         if not save or any(k not in KINDS for k in save):
             raise ValueError('ResultSaver: `save` must name some of %s, got %r' % (sorted(KINDS), save))
+        if png not in ('host', 'device'):
+            raise ValueError("ResultSaver: `png` must be 'host' or 'device', got %r" % (png,))
+        self.png = png
         workers = int(workers)
         if workers < 1:
             raise ValueError('ResultSaver: at least one worker thread (got %d)' % workers)
@@ -78,8 +86,16 @@ class ResultSaver(object):
             res = ops.flow_export(pred.contiguous(), valid, max_rad=self.max_rad, **{k: True for k in self.save})
             host = {}
             for k in self.save:
-                host[k] = slot.buffer(k, res[KINDS[k][2]])
-                host[k].copy_(res[KINDS[k][2]], non_blocking=True)
+                payload = res[KINDS[k][2]]
+                if self.png == 'device' and KINDS[k][1] == '.png':
+                    streams, lengths = ops.png_encode(payload)
+                    _, h, w, c = payload.shape
+                    host[k] = (slot.buffer(k + ' streams', streams), slot.buffer(k + ' lengths', lengths), (w, h, 8 * payload.element_size(), c))
+                    host[k][0].copy_(streams, non_blocking=True)
+                    host[k][1].copy_(lengths, non_blocking=True)
+                else:
+                    host[k] = slot.buffer(k, payload)
+                    host[k].copy_(payload, non_blocking=True)
             event = torch.cuda.Event()
             event.record()
             B = pred.shape[0]
@@ -95,6 +111,14 @@ class ResultSaver(object):
         try:
             event.synchronize()
             for k, buf in host.items():
+                if isinstance(buf, tuple):                                      # png='device': the zlib streams and their lengths
+                    streams, lengths, (w, h, depth, c) = buf[0].numpy(), buf[1].numpy(), buf[2]
+                    for i, name in enumerate(names):
+                        n = int(lengths[i])
+                        if n < 0:
+                            raise RuntimeError('ResultSaver: the device encoder\'s stream of %s did not fit its slot' % self.path(k, name))
+                        flow_io.write_png_stream(self.path(k, name), w, h, depth, c, streams[i, :n])
+                    continue
                 arr = buf.numpy()
                 for i, name in enumerate(names):
                     _WRITERS[k](self.path(k, name), arr[i])

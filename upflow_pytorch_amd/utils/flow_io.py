@@ -93,6 +93,22 @@ def write_png(filename, img, compression=3):
         f.write(_chunk(b'IEND', b''))
 
 
+def write_png_stream(filename, w, h, depth, channels, zstream):
+    """zstream: the complete zlib stream of the filtered scan lines of a w x h image of `channels` samples of `depth` bits — what
+    ops.png_encode leaves on the device (bytes, or a uint8 array) -> PNG: signature, IHDR, one IDAT (its CRC computed here), IEND."""
+    if depth not in (8, 16) or channels not in (1, 2, 3, 4) or w < 1 or h < 1:
+        raise ValueError('write_png_stream: depth 8 / 16 and 1..4 channels expected, got %dx%d, depth %r, %r channels' % (w, h, depth, channels))
+    ctype = {1: 0, 2: 4, 3: 2, 4: 6}[channels]
+    zstream = memoryview(np.ascontiguousarray(zstream, dtype=np.uint8) if isinstance(zstream, np.ndarray) else zstream)
+    with open(filename, 'wb') as f:
+        f.write(_PNG_SIG)
+        f.write(_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, depth, ctype, 0, 0, 0)))
+        f.write(struct.pack('>I', zstream.nbytes) + b'IDAT')
+        f.write(zstream)
+        f.write(struct.pack('>I', zlib.crc32(zstream, zlib.crc32(b'IDAT')) & 0xffffffff))
+        f.write(_chunk(b'IEND', b''))
+
+
 def _unfilter(raw, h, stride, bpp):
     out = np.zeros((h, stride), dtype=np.uint8)
     prev = np.zeros(stride, dtype=np.uint8)
