@@ -1790,3 +1790,284 @@ def blend_final_backward_ref(c):
     gx[:, 2] *= s * (1.0 - s)
     bound[:, 2] = bound[:, 2] * s * (1.0 - s) + 2 * U32 * np.abs(gx[:, 2])
     return gx, bound
+
+
+# ---- the default loss path: boundary-dilated warp, first-order smoothness, abs_robust, the distillation term -----------------------------
+# (csrc/loss.hip, loss_common.hpp, sgu_blend.hip msd_*; tests/test_hip_loss_exact.py)
+# Boundary warp.  The image holds integers in [-7, 7], flows multiples of 1/8, crop offsets multiples of 1/2 and upstream gradients
+# multiples of 1/4 in [-1, 1]: the positions are exact, every weight is a multiple of 1/64 (the product of two corner distances), every
+# product of the forward a multiple of 1/64 and of the backward a multiple of 1/32, and the sums of their absolute values stay far
+# below 2^24 quanta.  A correct kernel therefore equals the fp64 reference bit for bit in any operation order.
+BWARP_SHAPES = {'crop': (3, 3, 12, 16, 6, 8, 6), 'far': (1, 3, 23, 29, 17, 19, 20), 'full': (2, 3, 9, 7, 9, 7, 3),
+                'pixel': (1, 2, 5, 300, 1, 1, 2), 'frame1': (2, 1, 1, 1, 3, 5, 4)}          # B, C, Hi, Wi, h, w, flow reach in pixels
+BWARP_SHARE_CASES = ('crop', 'far', 'full')
+BWARP_CASES = tuple(BWARP_SHAPES) + ('edges',)
+BWARP_REACH = 64.0                                     # positions stay finite and within this many pixels of the frame
+BWARP_EDGES = (6, 9)                                   # Hi, Wi of the hand-built case
+
+
+def bwarp_ref(image, flow, start):
+    """oracle.ops.boundary_warp without its hard-coded .float(): grid + crop offset, + flow, floor, the corner indices clamped, four
+    gathers, weights from the CLAMPED corner coordinates.  The sample position is formed in the dtype of `flow` — it is the sum
+    (grid + offset) + flow of the stored values, rounded as the reference rounds it when the flow is fp32 — and everything after it
+    (corner distances, weights, products, sums) runs in the wider of the image's and the flow's dtypes.  All operands in fp64: the
+    whole chain in fp64; an fp64 image with the fp32 flow it was recorded with: the reference's positions, fp64 arithmetic.
+    Differentiable wrt the flow.  -> (out [B,C,h,w], geometry: x, y [B,h,w] and the clamped corners x0, x1, y0, y1 as int64)."""
+    pt = flow.dtype
+    dt = torch.promote_types(image.dtype, pt)
+    B, C, Hi, Wi = image.shape
+    h, w = flow.shape[2:]
+    xx = torch.arange(w, dtype=pt).view(1, 1, w)
+    yy = torch.arange(h, dtype=pt).view(1, h, 1)
+    start = start.to(pt).reshape(-1, 2)
+    if start.shape[0] == 1:
+        start = start.expand(B, 2)
+    x = ((xx + start[:, 0].view(B, 1, 1)) + flow[:, 0]).to(dt)
+    y = ((yy + start[:, 1].view(B, 1, 1)) + flow[:, 1]).to(dt)
+    x0r, y0r = torch.floor(x.detach()).long(), torch.floor(y.detach()).long()
+    x0, x1 = x0r.clamp(0, Wi - 1), (x0r + 1).clamp(0, Wi - 1)
+    y0, y1 = y0r.clamp(0, Hi - 1), (y0r + 1).clamp(0, Hi - 1)
+    flat = image.to(dt).reshape(B, C, Hi * Wi)
+
+    def tap(yi, xi):
+        return torch.gather(flat, 2, (yi * Wi + xi).view(B, 1, h * w).expand(B, C, h * w)).view(B, C, h, w)
+    x0f, x1f, y0f, y1f = x0.to(dt), x1.to(dt), y0.to(dt), y1.to(dt)
+    wa, wb = ((x1f - x) * (y1f - y)).unsqueeze(1), ((x1f - x) * (y - y0f)).unsqueeze(1)
+    wc, wd = ((x - x0f) * (y1f - y)).unsqueeze(1), ((x - x0f) * (y - y0f)).unsqueeze(1)
+    out = wa * tap(y0, x0) + wb * tap(y1, x0) + wc * tap(y0, x1) + wd * tap(y1, x1)
+    return out, dict(x=x.detach(), y=y.detach(), x0=x0, x1=x1, y0=y0, y1=y1)
+
+
+def bwarp_edge_targets(Hi, Wi):
+    """The sample positions (x, y) of the hand-built case, by kind."""
+    return {'integer': [(2.0, 3.0), (0.0, 0.0), (5.0, 1.0), (0.0, 4.0), (-1.0, 2.0), (float(Wi), 3.0), (3.0, -2.0)],
+            'last': [(Wi - 1.0, 2.0), (3.0, Hi - 1.0), (Wi - 1.0, Hi - 1.0), (Wi - 1.0, 1.5), (2.25, Hi - 1.0)],
+            'before': [(-0.5, 2.25), (-0.125, 0.0), (2.5, -0.25), (-0.875, -0.625), (3.0, -0.5)],
+            'after': [(Wi - 0.5, 1.5), (Wi - 0.125, 2.0), (1.125, Hi - 0.75), (Wi - 0.25, Hi - 0.375), (4.0, Hi - 0.5)]}
+
+
+@functools.lru_cache(maxsize=None)
+def bwarp_case(name):
+    """-> dict(image [B,C,Hi,Wi], flow [B,2,h,w], start [B,2,1,1] as (x, y), grad_out [B,C,h,w]), fp32 on the grids above.  'edges':
+    the first samples of a 4 x 8 crop sit on bwarp_edge_targets, the rest are drawn."""
+    gen = torch.Generator().manual_seed(seed_of('bwarp', name))
+    if name == 'edges':
+        (Hi, Wi), B, C, h, w, reach = BWARP_EDGES, 1, 3, 4, 8, 3
+    else:
+        B, C, Hi, Wi, h, w, reach = BWARP_SHAPES[name]
+    image = torch.randint(-7, 8, (B, C, Hi, Wi), generator=gen).float()
+    flow = grid((B, 2, h, w), 0.125, float(reach), gen)
+    # crop offsets: multiples of 1/2 with the crop inside the frame where it fits, item b half a pixel to the right of item b - 1's draw
+    sx = torch.randint(0, 2 * max(Wi - w, 0) + 1, (B,), generator=gen).double() * 0.5 + 0.5 * torch.arange(B, dtype=torch.float64)
+    sy = torch.randint(0, 2 * max(Hi - h, 0) + 1, (B,), generator=gen).double() * 0.5
+    start = torch.stack([sx, sy], 1).float().view(B, 2, 1, 1)
+    if name == 'edges':
+        start = torch.tensor([1.5, 0.5]).view(1, 2, 1, 1)
+        targets = [t for k in ('integer', 'last', 'before', 'after') for t in bwarp_edge_targets(Hi, Wi)[k]]
+        assert len(targets) <= h * w
+        for n, (tx, ty) in enumerate(targets):
+            i, j = divmod(n, w)
+            flow[0, 0, i, j] = tx - (j + 1.5)
+            flow[0, 1, i, j] = ty - (i + 0.5)
+    grad_out = grid((B, C, h, w), 0.25, 1.0, gen)
+    return dict(image=image, flow=flow, start=start, grad_out=grad_out)
+
+
+def bwarp_guard(c):
+    """The exactness conditions on the operands and the fp64 reference alone: the grids, positions within BWARP_REACH of the frame and
+    exact in fp32, weights multiples of 1/64, and the absolute products of the forward (quantum 1/64) and of the flow gradient (quantum
+    1/32) below 2^24 quanta.  -> (forward quanta, backward quanta, geometry)."""
+    image, flow, start, go = c['image'], c['flow'], c['start'], c['grad_out']
+    B, C, Hi, Wi = image.shape
+    assert on_grid(image, 1.0) and float(image.abs().max()) <= 7 and on_grid(flow, 0.125) and on_grid(start, 0.5)
+    assert on_grid(go, 0.25) and float(go.abs().max()) <= 1.0
+    assert B == 1 or len({tuple(s) for s in start.view(B, 2).tolist()}) == B, 'the crop offsets must differ from item to item'
+    _, g = bwarp_ref(image.double(), flow.double(), start.double())
+    x, y = g['x'], g['y']
+    assert torch.isfinite(x).all() and torch.isfinite(y).all()
+    assert float(x.min()) >= -BWARP_REACH and float(x.max()) <= Wi - 1 + BWARP_REACH
+    assert float(y.min()) >= -BWARP_REACH and float(y.max()) <= Hi - 1 + BWARP_REACH
+    assert torch.equal(x.float().double(), x) and torch.equal(y.float().double(), y)
+    ax, bx, ay, by = (g['x1'] - x).abs(), (x - g['x0']).abs(), (g['y1'] - y).abs(), (y - g['y0']).abs()
+    for wgt in (ax * ay, ax * by, bx * ay, bx * by):
+        assert on_grid(wgt, 1.0 / 64)
+    ia = image.double().abs().amax(1)                                            # (a bound per frame pixel over the channels)
+    amax = float(ia.max())
+    fwd = guard('boundary warp forward', (ax + bx) * (ay + by) * amax, 1.0 / 64)
+    bwd = guard('boundary warp flow gradient', C * float(go.abs().max()) * 2 * torch.maximum(ax + bx, ay + by) * amax, 1.0 / 32)
+    return fwd, bwd, g
+
+
+def bwarp_shares(c):
+    """-> (share of samples outside the frame, share on an integer coordinate, share of non-zero outputs), from the reference alone."""
+    B, C, Hi, Wi = c['image'].shape
+    out, g = bwarp_ref(c['image'].double(), c['flow'].double(), c['start'].double())
+    x, y = g['x'], g['y']
+    outside = (x < 0) | (x > Wi - 1) | (y < 0) | (y > Hi - 1)
+    integer = (x == x.round()) | (y == y.round())
+    return float(outside.double().mean()), float(integer.double().mean()), float((out != 0).double().mean())
+
+
+def bwarp_expected(c, channels=None):
+    """fp64 output and autograd flow gradient, rounded to fp32 (exact: the guard).  channels: an index list applied to the image's and
+    the upstream gradient's channel axis."""
+    image, go = c['image'].double(), c['grad_out'].double()
+    if channels is not None:
+        image, go = image[:, channels], go[:, channels]
+    flow = c['flow'].double().clone().requires_grad_(True)
+    out, _ = bwarp_ref(image, flow, c['start'].double())
+    (gf,) = torch.autograd.grad(out, flow, go)
+    assert torch.equal(out.detach().float().double(), out.detach()) and torch.equal(gf.float().double(), gf)
+    return out.detach().float(), gf.float()
+
+
+# First-order smoothness.  An image that is constant over the positions of each channel has zero differences, every edge weight is
+# exp(-0) = 1, and with `pred` on a grid of 1/4 both sums of absolute differences are integers of quanta: exact in fp32 in any order.
+SMOOTH1_SHAPES = [(2, 3, 2, 2), (2, 3, 2, 40), (2, 3, 40, 2), (2, 3, 37, 45), (1, 1, 545, 481)]       # the image's; pred has 2 channels
+SMOOTH1_GRID = (0.25, 2.0)
+LOSS_NT = 256                                          # loss::NT
+LOSS_MAX_BLOCKS = 1024
+
+
+def red_blocks(n):
+    """loss::red_blocks (csrc/loss_common.hpp): one workgroup per 256 elements, at most 1024."""
+    return max(1, min(LOSS_MAX_BLOCKS, (n + LOSS_NT - 1) // LOSS_NT))
+
+
+@functools.lru_cache(maxsize=None)
+def smooth1_exact_case(shape):
+    """-> dict(img [B,Ci,H,W], pred [B,2,H,W], total (sx, sy) exact, partials [nblocks, 2] exact fp64): workgroup b of
+    upf_loss_partials(n) takes the pixels p = b * 256 + t + k * nblocks * 256."""
+    B, Ci, H, W = shape
+    gen = torch.Generator().manual_seed(seed_of('smooth1', shape))
+    img = torch.rand(B, Ci, 1, 1, generator=gen).expand(B, Ci, H, W).contiguous()
+    pred = grid((B, 2, H, W), SMOOTH1_GRID[0], SMOOTH1_GRID[1], gen)
+    p64 = pred.double()
+    tx, ty = torch.zeros(B, H, W, dtype=torch.float64), torch.zeros(B, H, W, dtype=torch.float64)
+    tx[:, :-1, :] = (p64[:, :, :-1, :] - p64[:, :, 1:, :]).abs().sum(1)          # the term of pixel (i, j): its difference with (i+1, j)
+    ty[:, :, :-1] = (p64[:, :, :, :-1] - p64[:, :, :, 1:]).abs().sum(1)
+    total = (float(tx.sum()), float(ty.sum()))
+    assert on_grid(pred, SMOOTH1_GRID[0]) and float(pred.abs().max()) <= SMOOTH1_GRID[1]
+    assert max(total) / SMOOTH1_GRID[0] < LIMIT, 'smoothness %s: %.3g quanta' % (shape, max(total) / SMOOTH1_GRID[0])
+    n = B * H * W
+    nb = red_blocks(n)
+    p = np.arange(n)
+    owner = torch.from_numpy((p // LOSS_NT) % nb)
+    partials = torch.zeros(nb, 2, dtype=torch.float64)
+    partials[:, 0].index_add_(0, owner, tx.reshape(-1))
+    partials[:, 1].index_add_(0, owner, ty.reshape(-1))
+    return dict(img=img, pred=pred, total=total, partials=partials, nblocks=nb)
+
+
+# The distillation term, style 'upup' (csrc/sgu_blend.hip msd_*).
+MSD_MAXL, MSD_BAND_COLS, MSD_BAND_ROWS = 6, 512, 1024
+MSD_RATIO_LIMIT = 250                                  # ops.msd_upup_supported
+MSD_ROUTE_CASES = {'no_row_table': ((1030, 4), [(1, 2), (2, 2), (2, 4)]),
+                   'six_levels': ((40, 72), [(1, 2), (2, 3), (3, 5), (5, 9), (10, 18), (40, 72)]),
+                   'ratio_limit': ((6, 251), [(2, 2), (6, 2)]),
+                   'ragged_strips': ((9, 150), [(3, 70), (9, 130), (9, 150)]),
+                   'both_halves': ((12, 600), [(3, 9)])}
+MSD_DYADIC_CASES = {'dyadic_3': ((9, 17), [(3, 5), (5, 9), (9, 17)]),
+                    'dyadic_6': ((33, 65), [(2, 2), (3, 5), (5, 9), (9, 17), (17, 33), (33, 65)])}
+MSD_BATCHES = ((1, True), (3, False))                  # (B, masked)
+MSD_WEIGHT = 0.7
+MSD_TORCH32_CAP = 2e-4                                 # a route case whose own fp32 torch gradient error passes this is drawn again
+# Two draws were replaced by better-conditioned ones that reach the same route (seeds unchanged: seed_of('msd', name, B, masked)):
+#   'away'   the first draw put label pixels so close to the up-sampled (3, 70) level that the fp32 composition's own gradient error
+#            against fp64 was 2.2e-4, past MSD_TORCH32_CAP (near d = 0 the derivative of (|d| + eps)^(q-1) multiplies the rounding of d by
+#            ~1e3).  The label now keeps |y| >= 3 and the levels are N(0, 1/16): no |d| near 0.
+#   'signed' the vertical rate is 515, and the up-sampled (2, 2) level crossed the label in the second component.  There the fp32
+#            position chain ALONE (msd_chain_grads: everything else in fp64) is 7.2e-6 from fp64, while torch's fp32 composition happened
+#            to land at 2.7e-6, a bound of 6.7e-6: the rule asked more than the chain it shares with the kernel can give.  Each level plane
+#            now has one sign and magnitudes in [0.5, ...): rate x level stays far from the label in the second component.
+# tests/test_exact_model_cpu.py asserts both conditions for every case: the cap, and chain error <= bound.
+MSD_REDRAWN = {('ragged_strips', 3, False): 'away', ('no_row_table', 3, False): 'signed'}
+
+
+def msd_ref(levels, y, occ=None, weight=1.0, q=0.4, eps=0.01):
+    """The torch composition of the term in the dtype it is given: F.interpolate(bilinear, align_corners=True) times [W/w, H/h],
+    (|. - y| + eps)^q, the masked sum over (sum occ + 1e-6) or the plain mean, summed over the levels, times weight."""
+    H, W = y.shape[2:]
+    total = 0
+    for x in levels:
+        h, w = x.shape[2:]
+        up = F.interpolate(x, size=(H, W), mode='bilinear', align_corners=True)
+        up = up * torch.tensor([W / w, H / h], dtype=x.dtype).view(1, 2, 1, 1)
+        d = ((up - y).abs() + eps).pow(q)
+        total = total + ((d * occ).sum() / (occ.sum() + 1e-6) if occ is not None else d.mean())
+    return weight * total
+
+
+def msd_cases():
+    """-> [(name, B, masked)]: every route and dyadic case with B = 1 under a mask and B = 3 without."""
+    return [(n, B, m) for n in list(MSD_ROUTE_CASES) + list(MSD_DYADIC_CASES) for B, m in MSD_BATCHES]
+
+
+@functools.lru_cache(maxsize=None)
+def msd_case(name, B, masked):
+    """-> (levels [B,2,h,w] ..., y [B,2,H,W], occ [B,1,H,W] or None), fp32: normal deviates (the label times 3, the levels times 1/2),
+    or multiples of 1/4 within +-4 for the dyadic cases."""
+    dyadic = name in MSD_DYADIC_CASES
+    (H, W), sizes = (MSD_DYADIC_CASES if dyadic else MSD_ROUTE_CASES)[name]
+    gen = torch.Generator().manual_seed(seed_of('msd', name, B, masked))
+    if dyadic:
+        y = grid((B, 2, H, W), RESIZE_GRID[0], RESIZE_GRID[1], gen)
+        levels = [grid((B, 2, h, w), RESIZE_GRID[0], RESIZE_GRID[1], gen) for h, w in sizes]
+        assert all(is_dyadic_ratio(h, H) and is_dyadic_ratio(w, W) for h, w in sizes)
+    else:
+        y = 3.0 * torch.randn(B, 2, H, W, generator=gen)
+        levels = [0.5 * torch.randn(B, 2, h, w, generator=gen) for h, w in sizes]
+        redrawn = MSD_REDRAWN.get((name, B, masked))
+        if redrawn == 'away':
+            y = torch.sign(y) * (3.0 + y.abs())
+            levels = [0.5 * x for x in levels]
+        elif redrawn == 'signed':
+            levels = [torch.sign(x[:, :, :1, :1]) * (0.5 + x.abs()) for x in levels]
+    occ = (torch.rand(B, 1, H, W, generator=gen) > 0.3).float() if masked else None
+    return levels, y, occ
+
+
+def msd_chain_grads(levels, y, occ=None, weight=1.0, q=0.4, eps=0.01):
+    """The gradients of msd_ref with the reference's fp32 POSITION CHAIN (lerp32: the weights torch's fp32 resize and the kernels
+    share, bit for bit) and everything else in fp64: what separates the error of the geometry from that of the arithmetic.  No fp32
+    implementation that follows the chain can be expected closer to fp64 than this, except by luck.  -> one fp64 array per level."""
+    yn = y.double().numpy()
+    B, _, H, W = yn.shape
+    on = None if occ is None else occ.double().numpy()
+    den = float(on.sum() + 1e-6) if on is not None else float(B * 2 * H * W)
+    out = []
+    for x in levels:
+        xn = x.double().numpy()
+        h, w = xn.shape[2:]
+        rate = np.array([W / w, H / h]).reshape(1, 2, 1, 1)
+        up, _ = resize_forward_ref(xn, H, W, False)
+        d = up * rate - yn
+        t = q * (np.abs(d) + eps) ** (q - 1.0) * np.sign(d)
+        if on is not None:
+            t = t * on
+        out.append(np.einsum('ia,ncij,jb->ncab', lerp_matrix(H, h), t, lerp_matrix(W, w)) * rate * (weight / den))
+    return out
+
+
+def msd_route(sizes, H, W, B=1):
+    """msd_levels and msd_bwd_kernel of csrc/sgu_blend.hip read in Python.  -> None where the entry point refuses (a level count
+    outside 1..6, a level narrower than 2 or larger than the label, a strip width below 1), else one dict per level: NB (level columns
+    per strip), strips (per row), blocks (workgroups), row_table (the footprint rows fit BAND_ROWS), second_half (a strip's label
+    columns pass 256, so the second column of a thread is used), span (the widest strip in label columns; the kernel's LDS rows hold
+    BAND_COLS)."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    if not (1 <= len(sizes) <= MSD_MAXL and H > 1 and W > 1):
+        return None
+    out = []
+    for h, w in sizes:
+        if not (h >= 1 and w >= 2 and h <= H and w <= W):
+            return None
+        inv = (W - 1) / (w - 1)
+        NB = min(int((MSD_BAND_COLS - 8) / inv) - 1, 64, w)
+        if NB < 1:
+            return None
+        strips = cdiv(w, NB)
+        rows = max(_bwd_range(a, h, H)[1] - _bwd_range(a, h, H)[0] + 1 for a in range(h))
+        span = max(_bwd_range(min(w, b0 + NB) - 1, w, W)[1] - _bwd_range(b0, w, W)[0] + 1 for b0 in range(0, w, NB))
+        out.append(dict(NB=NB, strips=strips, blocks=B * h * strips, row_table=rows <= MSD_BAND_ROWS, second_half=span > 256, span=span))
+    return out

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 import _exact_model as em
+import _lossvar as lv
 from conftest import GOLDEN, load_golden, unpack_mask
 
 DT = [pytest.param(d, id=em.DTYPE_NAMES[d]) for d in em.DTYPES]
@@ -726,3 +727,163 @@ def test_census_model_is_the_adjoint_and_its_cases_are_what_they_claim():
                     # the bound is a small fraction of the gradient: a missing family of terms (the neighbour role) cannot hide in it
                     assert np.abs(ref['gg1']).max() > 100 * ref['b_gg1'].max()
     assert 2 < 2 * min(em.CENSUS_R) + 1 and 17 * 65 > 256                                 # an image smaller than the window; two workgroups
+
+
+# ---- the default loss path (tests/test_hip_loss_exact.py) ---------------------------------------------------------------------------------
+def _msd_eval(name, B, masked, dtype):
+    levels, y, occ = em.msd_case(name, B, masked)
+    xs = [x.to(dtype).clone().requires_grad_(True) for x in levels]
+    v = em.msd_ref(xs, y.to(dtype), None if occ is None else occ.to(dtype), em.MSD_WEIGHT)
+    return v.detach(), torch.autograd.grad(v, xs)
+
+
+def test_boundary_warp_cases_hold_the_guard_and_the_shares():
+    """Every case is on its grids and below 2^24 quanta, the fp32 oracle equals the fp64 restatement bit for bit (output and autograd
+    flow gradient), and the matrix is not vacuous: samples outside the frame, on integer coordinates, non-zero outputs."""
+    from oracle import ops as oracle_ops
+    for name in em.BWARP_CASES:
+        c = em.bwarp_case(name)
+        fwd, bwd, g = em.bwarp_guard(c)
+        assert fwd < em.LIMIT and bwd < em.LIMIT
+        out, gf = em.bwarp_expected(c)
+        flow = c['flow'].clone().requires_grad_(True)
+        o32 = oracle_ops.boundary_warp(c['image'], flow, c['start'])
+        (g32,) = torch.autograd.grad(o32, flow, c['grad_out'])
+        assert torch.equal(o32.detach(), out) and torch.equal(g32, gf), name
+        if name in em.BWARP_SHARE_CASES:
+            outside, integer, nonzero = em.bwarp_shares(c)
+            print(name, 'outside %.2f, on an integer coordinate %.2f, non-zero outputs %.2f' % (outside, integer, nonzero))
+            assert 0.2 <= outside <= 0.8 and integer >= 0.1 and nonzero >= 0.25, (name, outside, integer, nonzero)
+            assert gf.abs().max() > 0
+    B, C, Hi, Wi, h, w, _ = em.BWARP_SHAPES['far']
+    assert h * w == 323 and h * w > em.LOSS_NT and h * w % em.LOSS_NT != 0                # two workgroups, the second ragged
+    _, _, g = em.bwarp_guard(em.bwarp_case('far'))
+    assert g['x'].min() < -1 and g['x'].max() > Wi and g['y'].min() < -1 and g['y'].max() > Hi          # far outside on all four sides
+    c = em.bwarp_case('frame1')                                                           # a one-pixel frame: every corner clamps to it
+    out, gf = em.bwarp_expected(c)
+    assert not out.any() and not gf.any()
+    c = em.bwarp_case('full')
+    assert c['image'].shape[2:] == c['flow'].shape[2:]
+
+
+def test_boundary_warp_hand_built_case_is_what_it_claims():
+    c = em.bwarp_case('edges')
+    Hi, Wi = em.BWARP_EDGES
+    assert tuple(c['image'].shape[2:]) == (Hi, Wi)
+    out, _ = em.bwarp_expected(c)
+    _, _, g = em.bwarp_guard(c)
+    w = c['flow'].shape[3]
+    n = 0
+    for kind, targets in em.bwarp_edge_targets(Hi, Wi).items():
+        for tx, ty in targets:
+            i, j = divmod(n, w)
+            n += 1
+            x, y = float(g['x'][0, i, j]), float(g['y'][0, i, j])
+            assert (x, y) == (tx, ty), (kind, (tx, ty), (x, y))
+            if kind == 'integer':
+                assert x == round(x) and y == round(y)
+            if kind == 'last':                                                            # both corners of one axis clamp to one pixel: weights cancel
+                assert x == Wi - 1 or y == Hi - 1
+                assert not out[0, :, i, j].any(), (tx, ty)
+            if kind == 'before':
+                assert -1 < x < 0 or -1 < y < 0
+            if kind == 'after':
+                assert Wi - 1 < x < Wi or Hi - 1 < y < Hi
+    inside = [(2.0, 3.0), (5.0, 1.0)]                                                      # integer positions inside: the pixel itself
+    for k, (tx, ty) in enumerate(em.bwarp_edge_targets(Hi, Wi)['integer']):
+        if (tx, ty) in inside:
+            i, j = divmod(k, w)
+            assert torch.equal(out[0, :, i, j], c['image'][0, :, int(ty), int(tx)])
+
+
+@pytest.mark.parametrize('i', range(3))
+def test_bwarp_ref_in_fp64_matches_the_golden_fixtures(i):
+    """fp64 arithmetic on the fixtures' operands as recorded, within the fixtures' own tolerances (1e-6 on the output, 1e-5 on the flow
+    gradient).  The flow is handed over in the fp32 it was recorded in, so bwarp_ref forms the sample positions as the reference formed
+    them — (grid + offset) + flow, rounded to fp32 — and runs everything after them in fp64: measured 5.3e-8 / 1.0e-7 / 2.0e-8 on the
+    output, 2.4e-7 / 4.8e-7 / 6.0e-8 on the gradient.  With the flow promoted to fp64 first the positions are other numbers than the
+    recorded ones (up to 55.9 in fixture 0: half an fp32 ulp is 1.9e-6 of a pixel), and the same comparison gives 1.7e-6 / 8.4e-7 /
+    1.1e-7 and 5.7e-6 / 2.8e-6 / 8.2e-8 (printed; the exact cases of the GPU file sit on grids where the two positions coincide)."""
+    g = load_golden('bwarp_%d' % i)
+    flow = g['flow'].clone().requires_grad_(True)
+    out, geo = em.bwarp_ref(g['image'].double(), flow, g['start'])
+    assert out.dtype == torch.float64 and geo['x'].dtype == torch.float64
+    e_out = float((out.detach() - g['out'].double()).abs().max())
+    (gf,) = torch.autograd.grad(out, flow, g['grad_out'].double())
+    e_gf = float((gf.double() - g['gflow'].double()).abs().max())
+    flow64 = g['flow'].double().clone().requires_grad_(True)
+    out64, _ = em.bwarp_ref(g['image'].double(), flow64, g['start'].double())
+    (gf64,) = torch.autograd.grad(out64, flow64, g['grad_out'].double())
+    print('bwarp_%d: fp64 arithmetic on the recorded positions: output %.3g, gradient %.3g; positions in fp64 too: %.3g, %.3g'
+          % (i, e_out, e_gf, float((out64.detach() - g['out'].double()).abs().max()), float((gf64 - g['gflow'].double()).abs().max())))
+    assert e_out <= 1e-6 and e_gf <= 1e-5
+
+
+@pytest.mark.parametrize('i', range(3))
+def test_bwarp_ref_in_fp32_gives_the_golden_fixtures_bits(i):
+    g = load_golden('bwarp_%d' % i)
+    flow = g['flow'].clone().requires_grad_(True)
+    out, _ = em.bwarp_ref(g['image'], flow, g['start'])
+    (gf,) = torch.autograd.grad(out, flow, g['grad_out'])
+    assert out.dtype == torch.float32 and torch.equal(out.detach(), g['out']) and torch.equal(gf, g['gflow'])
+
+
+def test_smooth1_exact_cases_partials_and_totals():
+    from oracle import ops as oracle_ops
+    assert em.SMOOTH1_SHAPES[-1][2] * em.SMOOTH1_SHAPES[-1][3] == em.LOSS_MAX_BLOCKS * em.LOSS_NT + 1
+    assert [em.red_blocks(n) for n in (1, 256, 257, 262144, 262145, 10 ** 7)] == [1, 1, 2, 1024, 1024, 1024]
+    for shape in em.SMOOTH1_SHAPES:
+        B, Ci, H, W = shape
+        c = em.smooth1_exact_case(shape)
+        assert c['nblocks'] == em.red_blocks(B * H * W) and tuple(c['partials'].shape) == (c['nblocks'], 2)
+        assert (c['img'] == c['img'][:, :, :1, :1]).all() and len(set(c['img'][:, :, 0, 0].reshape(-1).tolist())) == B * Ci
+        assert max(c['total']) / em.SMOOTH1_GRID[0] < em.LIMIT
+        assert tuple(c['partials'].sum(0).tolist()) == c['total'] and c['total'][0] > 0 and c['total'][1] > 0
+        assert torch.equal(c['partials'].float().double(), c['partials'])
+        assert (c['partials'].sum(1) > 0).all()                                              # every workgroup has work
+        v = oracle_ops.smooth_edge1(c['img'].double(), c['pred'].double())                 # exp(-0) = 1: the mean of the differences
+        want = c['total'][0] / (B * 2 * (H - 1) * W) + c['total'][1] / (B * 2 * H * (W - 1))
+        assert abs(float(v) - want) <= 1e-12 * want
+    # the last pixel of the largest shape is the second element of workgroup 0's first thread; it has no lower or right neighbour
+    c = em.smooth1_exact_case(em.SMOOTH1_SHAPES[-1])
+    assert c['nblocks'] == em.LOSS_MAX_BLOCKS
+
+
+def test_msd_routes_are_the_named_ones():
+    r = {n: em.msd_route(sizes, H, W) for n, ((H, W), sizes) in list(em.MSD_ROUTE_CASES.items()) + list(em.MSD_DYADIC_CASES.items())}
+    assert all(v is not None and all(l['span'] <= em.MSD_BAND_COLS and l['NB'] >= 1 for l in v) for v in r.values())
+    assert all(not l['row_table'] for l in r['no_row_table']) and all(l['row_table'] for n, v in r.items() if n != 'no_row_table' for l in v)
+    assert len(r['six_levels']) == em.MSD_MAXL == len(r['dyadic_6']) and em.MSD_ROUTE_CASES['six_levels'][1][0][0] == 1        # a one-row level
+    (H, W), sizes = em.MSD_ROUTE_CASES['ratio_limit']
+    assert all((W - 1) / (w - 1) == em.MSD_RATIO_LIMIT for _, w in sizes) and all(l['NB'] == 1 and l['strips'] == 2 for l in r['ratio_limit'])
+    assert [(l['NB'], l['strips']) for l in r['ragged_strips']] == [(64, 2), (64, 3), (64, 3)]
+    assert all(w > 64 and w % 64 for _, w in em.MSD_ROUTE_CASES['ragged_strips'][1])
+    assert [l['second_half'] for l in r['both_halves']] == [True] and r['both_halves'][0]['strips'] == 2
+    assert not any(l['second_half'] for n, v in r.items() if n != 'both_halves' for l in v)
+    # the entry point's refusals: a strip width of 0, a level narrower than 2, seven levels, a level larger than the label
+    assert em.msd_route([(2, 2)], 6, 253) is not None and em.msd_route([(2, 2)], 6, 254) is None
+    assert em.msd_route([(2, 1)], 6, 9) is None and em.msd_route([(2, 2)] * 7, 6, 9) is None and em.msd_route([(7, 2)], 6, 9) is None
+    assert {(B, m) for _, B, m in em.msd_cases()} == {(1, True), (3, False)} and len(em.msd_cases()) == 14
+
+
+def test_msd_reference_fp32_error_is_nonzero_and_capped():
+    """The rule's right-hand side exists for every case (the fp32 composition differs from fp64), no route case's own fp32 gradient
+    error passes MSD_TORCH32_CAP, and the rule can be met: the fp32 position chain alone (msd_chain_grads, shared bit for bit by torch's
+    fp32 resize and the kernels) stays within the bound.  The dyadic cases sit on their grid, where the chain is exact."""
+    for name, B, masked in em.msd_cases():
+        levels, y, occ = em.msd_case(name, B, masked)
+        assert (occ is not None) == masked and y.shape[0] == B and (occ is None or 0 < float(occ.mean()) < 1)
+        (v32, g32), (v64, g64) = _msd_eval(name, B, masked, torch.float32), _msd_eval(name, B, masked, torch.float64)
+        errs = [lv.relerr(a, b) for a, b in zip(g32, g64)]
+        print(name, B, masked, 'value %.3g' % lv.relerr(v32, v64), 'gradients', ' '.join('%.3g' % e for e in errs))
+        assert lv.relerr(v32, v64) > 0 and all(e > 0 for e in errs)
+        assert max(errs) <= em.MSD_TORCH32_CAP, (name, B, masked, errs)
+        assert all(float(g.abs().max()) > 0 for g in g64)
+        chain = [lv.relerr(torch.from_numpy(c), b) for c, b in zip(em.msd_chain_grads(levels, y, occ, em.MSD_WEIGHT), g64)]
+        bounds = [lv.bound(a, b) for a, b in zip(g32, g64)]
+        print('    position chain alone', ' '.join('%.3g' % e for e in chain), ' bounds', ' '.join('%.3g' % e for e in bounds))
+        assert all(e <= b for e, b in zip(chain, bounds)), (name, B, masked, chain, bounds)
+        if name in em.MSD_DYADIC_CASES:
+            assert all(em.on_grid(t, em.RESIZE_GRID[0]) and float(t.abs().max()) <= em.RESIZE_GRID[1] for t in levels + [y])
+            assert max(errs) <= 1e-5 and max(chain) <= 1e-12                               # exact positions: a small bound
+    assert set(em.MSD_REDRAWN) <= {c for c in em.msd_cases() if c[0] in em.MSD_ROUTE_CASES}
