@@ -229,20 +229,22 @@ class Arena(object):
         self.buf = torch.full((elems,), float('nan'), dtype=dtype, device=self.device)
         self.cur = 0
 
-    def _take(self, n, lead, align):
-        """n elements for a block whose view starts `lead` elements in; the view start is a multiple of `align` elements."""
+    def _take(self, n, lead, align, skew=0):
+        """n elements for a block whose view starts `lead` elements in; the view start is `skew` elements past a multiple of `align`
+        elements."""
         start = self.cur + self.MARGIN
-        start += (-(start + lead)) % align
+        start += (skew - (start + lead)) % align
         assert start + n + self.MARGIN <= self.buf.numel(), 'arena too small'
         self.cur = start + n
         return self.buf[start:start + n]
 
-    def nchw(self, B, C, H, W, before=1, after=1, pitch=None, align=1, fill=None):
-        """[B,C,H,W] channel slice of a [B, before + C + after, H, pitch] block (pitch > W: rows with NaN pitch columns)."""
+    def nchw(self, B, C, H, W, before=1, after=1, pitch=None, align=1, fill=None, skew=0):
+        """[B,C,H,W] channel slice of a [B, before + C + after, H, pitch] block (pitch > W: rows with NaN pitch columns); its first
+        element `skew` elements past a multiple of `align` elements."""
         assert before >= 1 and after >= 1
         p = W if pitch is None else pitch
         planes = before + C + after
-        blk = self._take(B * planes * H * p, before * H * p, align).view(B, planes, H, p)
+        blk = self._take(B * planes * H * p, before * H * p, align, skew).view(B, planes, H, p)
         v = blk[:, before:before + C, :, :W]
         if fill is not None:
             v.copy_(fill.to(self.dtype))
@@ -2071,3 +2073,314 @@ def msd_route(sizes, H, W, B=1):
         span = max(_bwd_range(min(w, b0 + NB) - 1, w, W)[1] - _bwd_range(b0, w, W)[0] + 1 for b0 in range(0, w, NB))
         out.append(dict(NB=NB, strips=strips, blocks=B * h * strips, row_table=rows <= MSD_BAND_ROWS, second_half=span > 256, span=span))
     return out
+
+
+# ---- the split-precision fp32 convolutions (csrc/conv_x3.hip, conv_x3_bwd.hip; tests/test_hip_conv_x3_exact.py) ---------------------
+# Operands on a TWO-LEVEL grid: a coarse base (x, grad_y: integers in [-2, 2]; w: 2^-5 * {-1, 0, 0, 1}) and, on two thirds of the
+# elements with a non-zero base, a fine part of +-2^-13 of the base unit.  The fine part is below half an fp16 ulp of the base in both
+# directions, so fp16(a) is the base and fp16(a - fp16(a)) the fine part: the split of tests/_x3_model.py is lossless and every
+# operand enters the matrix cores as two exact halves with a NON-ZERO low half.  Every product of two halves is exact in fp32; the
+# products hi * hi are multiples of the cross products' quantum (unit_a * unit_b * 2^-13); with the sum of the absolute values of all
+# three products (and the bias) below 2^24 quanta every partial sum of every order is exact, and a correct kernel's output is ONE
+# value: the fp64 sum hi*hi + lo*hi + hi*lo of _x3_model (the lo * lo product dropped, as include/upflow_hip.h documents), plus the
+# bias, un-scaled by exact powers of two.  The per-tensor scales (x3_scale_of: the weights at pack time, grad_pre in upf_act_grad_x3)
+# are powers of two: they move the quantum along with the operands and change nothing in the count.
+import _x3_model as xm
+
+X3_FINE = 2.0 ** -13
+X3_XBASE = (-2.0, -1.0, 0.0, 1.0, 2.0)
+X3_WBASE = (-1.0, 0.0, 0.0, 1.0)
+X3_WUNIT = 2.0 ** -5
+
+
+def x3_values(shape, bases, unit, gen, lo=None):
+    """fp32 CPU tensor of (base + fine * 2^-13) * unit; fine in {-1, 0, 1}, only where the base is non-zero and (lo, a broadcastable
+    bool tensor) allows a low half."""
+    base = torch.tensor(bases, dtype=torch.float64)[torch.randint(0, len(bases), shape, generator=gen)]
+    fine = torch.randint(-1, 2, shape, generator=gen).double() * (base != 0)
+    if lo is not None:
+        fine = fine * lo
+    v = (base + fine * X3_FINE) * unit
+    assert torch.equal(v.float().double(), v)
+    return v.float()
+
+
+def _parity(n, odd):
+    return (torch.arange(n) % 2 == 1) if odd else (torch.arange(n) % 2 == 0)
+
+
+def x3_operands(layer, zeros=True, lo='all', x_pow2=0, w_pow2=0, salt=0):
+    """-> dict x, w, b, gy (fp32 CPU) and their units.  zeros: exact zeros among the pre-activations — output channel Cout // 2 with zero
+    weights and a zero bias where Cout >= 4 (a whole channel of them); for a narrower layer (a dead channel would be a third or half
+    of its outputs) the corner instead: x is zero on the receptive field of output pixel (0, 0) and b[0] = 0, so pre[:, 0, 0, 0] = 0.
+    lo = 'disjoint': no multiplied pair has two non-zero low halves — x and grad_y carry theirs on even channels, w on odd (ci, co):
+    the three-product model then IS the plain fp64 convolution of the fp32 operands.
+    x_pow2 / w_pow2: x (w) and the bias times that power of two (the scale-invariance cases)."""
+    gen = torch.Generator().manual_seed(seed_of('x3', layer.name, salt))
+    ho, wo = layer.out_hw
+    ux, uw = 2.0 ** x_pow2, X3_WUNIT * 2.0 ** w_pow2
+    dis = lo == 'disjoint'
+    x = x3_values((layer.B, layer.Cin, layer.H, layer.W), X3_XBASE, ux, gen, _parity(layer.Cin, False).view(1, -1, 1, 1) if dis else None)
+    w = x3_values((layer.Cout, layer.Cin, layer.k, layer.k), X3_WBASE, uw, gen,
+                  (_parity(layer.Cout, True).view(-1, 1, 1, 1) & _parity(layer.Cin, True).view(1, -1, 1, 1)) if dis else None)
+    ub = ux * uw / X3_WUNIT * X3_FINE                 # bias: multiples of 2^-13 within [-2, 2] (times the powers of two of x and w)
+    b = (torch.randint(-2 ** 14, 2 ** 14 + 1, (layer.Cout,), generator=gen).double() * ub).float()
+    gy = x3_values((layer.B, layer.Cout, ho, wo), X3_XBASE, 1.0, gen, _parity(layer.Cout, False).view(1, -1, 1, 1) if dis else None)
+    if zeros and layer.Cout >= 4:
+        w[layer.Cout // 2] = 0
+        b[layer.Cout // 2] = 0
+    elif zeros:
+        reach = 1 if layer.k == 1 else (2 if layer.s == 2 else layer.d + 1)
+        step = 1 if (layer.k == 1 or layer.s == 2) else layer.d
+        x[:, :, 0:reach:step, 0:reach:step] = 0
+        b[0] = 0
+    return {'x': x, 'w': w, 'b': b, 'gy': gy, 'ux': ux, 'uw': uw, 'ub': ub}
+
+
+def _x3_halves(t, unit, what):
+    """Guard (a): _x3_model.split reproduces the operand; its halves sit on the grids `unit` and `unit * 2^-13`."""
+    hi, lo = xm.split(t)
+    assert torch.equal(hi + lo, t.double()), '%s: the fp16 split is not lossless' % what
+    assert on_grid(hi, unit) and on_grid(lo, unit * X3_FINE), '%s: a half is off its grid' % what
+    return hi, lo
+
+
+def x3_products(contract, a, ua, b, ub, what):
+    """The three products of one operand pair as the kernels form them: a (unit ua), b (unit ub) fp32 tensors as the kernel splits
+    them (scaled where it scales them); contract(p, q) the fp64 contraction.  -> dict sum (fp64), abs (the contraction of the absolute
+    halves), lh / hl (the two cross products), lolo (what the dropped product would be), q (the quantum)."""
+    ah, al = _x3_halves(a, ua, what + ' first operand')
+    bh, bl = _x3_halves(b, ub, what + ' second operand')
+    lh, hl = contract(al, bh), contract(ah, bl)
+    return {'sum': contract(ah, bh) + lh + hl, 'lh': lh, 'hl': hl, 'lolo': contract(al.abs(), bl.abs()),
+            'abs': contract(ah.abs(), bh.abs()) + contract(al.abs(), bh.abs()) + contract(ah.abs(), bl.abs()), 'q': ua * ub * X3_FINE}
+
+
+def x3_exact32(v64, what):
+    """Guard (c)."""
+    assert torch.equal(v64.float().double(), v64), '%s: the reference is not exact in fp32' % what
+    return v64
+
+
+def x3_cross_share(p):
+    """Guard (d): the share of output elements in which each cross product is non-zero."""
+    n = max(p['lh'].numel(), 1)
+    return min(float((p['lh'] != 0).sum()) / n, float((p['hl'] != 0).sum()) / n)
+
+
+def x3_scaled_w(w):
+    """-> (w * 2^s as fp32, 2^s): what upf_conv_x3_pack_weights splits."""
+    scw = xm.scale_of(float(w.abs().max()))
+    ws = w.double() * scw
+    assert torch.equal(ws.float().double(), ws)
+    return ws.float(), scw
+
+
+def x3_act(pre, slope):
+    return act(pre, slope)
+
+
+def x3_forward_ref(o, layer, what='x3 forward'):
+    """-> dict pre (fp64, un-scaled), top (largest sum of absolute terms in quanta), share (guard d), plain (model == the plain fp64
+    convolution: true where no pair has two low halves).  Guards (a), (b), (c) inside."""
+    g = geom(layer.k, layer.d, layer.s)
+    ws, scw = x3_scaled_w(o['w'])
+    p = x3_products(lambda a, c: F.conv2d(a, c, None, **g), o['x'], o['ux'], ws, o['uw'] * scw, what)
+    bs = o['b'].double() * scw
+    top = guard(what, p['abs'] + bs.abs().view(1, -1, 1, 1), p['q'], (bs, o['ub'] * scw))
+    pre = x3_exact32((p['sum'] + bs.view(1, -1, 1, 1)) / scw, what)
+    plain = F.conv2d(o['x'].double(), o['w'].double(), o['b'].double(), **g)
+    return {'pre': pre, 'top': top, 'share': x3_cross_share(p), 'plain': bool(torch.equal(pre, plain)), 'nolo': float(p['lolo'].max()) == 0.0}
+
+
+def x3_act_grad_ref(gy, pre, slope, ug=1.0, what='x3 act_grad'):
+    """upf_act_grad_x3 -> dict gpre (fp32), gs (fp32), sc (2^s), max (max |gpre|), ug (the unit of gs's hi half).  pre None: no
+    activation.  The mask is `y > 0`: exact zeros take the slope."""
+    mask = None if (pre is None or not slope) else pre > 0
+    gpre, gs, sc = xm.act_grad(gy, mask, slope)
+    assert torch.equal(gs.double(), gpre.double() * sc)
+    u = ug * sc * (slope if mask is not None else 1.0)
+    _x3_halves(gs, u, what)
+    return {'gpre': gpre, 'gs': gs, 'sc': sc, 'max': float(gpre.abs().max()), 'ug': u}
+
+
+def x3_bias_runs(gs, runs=32):
+    """The first-stage bias sums of upf_act_grad_x3 as csrc/conv_x3_bwd.hip run_of_block cuts them: the B * HW elements of a channel in
+    (n, pixel) order, `runs` runs of ceil(B * HW / runs).  -> [C, runs] fp64."""
+    B, C = gs.shape[:2]
+    flat = gs.double().permute(1, 0, 2, 3).reshape(C, -1)
+    per = -(-flat.shape[1] // runs)
+    flat = F.pad(flat, (0, runs * per - flat.shape[1]))
+    return flat.view(C, runs, per).sum(2)
+
+
+def x3_dgrad_ref(ag, o, layer, what='x3 data gradient'):
+    """upf_conv_x3_dgrad from x3_act_grad_ref's result.  Stride 1: the three products of gs with the scaled, split weights, un-scaled
+    by both powers of two.  Stride 2: the plain fp32 kernel on the master weights — exact only where no pair has two low halves
+    (asserted).  -> dict gx (fp64), top, share."""
+    g = geom(layer.k, layer.d, layer.s)
+    shape = (layer.B, layer.Cin, layer.H, layer.W)
+    con = lambda a, c: torch.nn.grad.conv2d_input(shape, c, a, **g)
+    if layer.s == 2:
+        p = x3_products(con, ag['gs'], ag['ug'], o['w'], o['uw'], what)
+        assert float(p['lolo'].max()) == 0.0, '%s: the plain fp32 kernel needs pairs without two low halves' % what
+        top = guard(what, p['abs'], p['q'])
+        return {'gx': x3_exact32(p['sum'] / ag['sc'], what), 'top': top, 'share': x3_cross_share(p)}
+    ws, scw = x3_scaled_w(o['w'])
+    p = x3_products(con, ag['gs'], ag['ug'], ws, o['uw'] * scw, what)
+    top = guard(what, p['abs'], p['q'])
+    return {'gx': x3_exact32(p['sum'] / scw / ag['sc'], what), 'top': top, 'share': x3_cross_share(p), 'nolo': float(p['lolo'].max()) == 0.0}
+
+
+def x3_wgrad_ref(uses, w_shape, d, s, ux=1.0, what='x3 weight gradient'):
+    """upf_conv_x3_wgrad over uses [(x, act-grad dict or (grad_pre fp32, unit) for a NULL-slot use)]: per level the three products of
+    gs (grad_pre as it is for a NULL slot) with x split un-scaled, times the level's 2^-s; the bias gradient = the levels' sums of gs,
+    each times its 2^-s.  The guard counts everything in the FINEST level's quantum.  -> dict gw, gb (fp64), top, top_b, share."""
+    k = w_shape[-1]
+    g = geom(k, d, s)
+    gw, gb, ab, abb, q, qb, nolo = 0.0, 0.0, 0.0, 0.0, float('inf'), float('inf'), True
+    cross = {'lh': 0.0, 'hl': 0.0}
+    for x, a in uses:
+        gs, u, sc = (a['gs'], a['ug'], a['sc']) if isinstance(a, dict) else (a[0], a[1], 1.0)
+        p = x3_products(lambda t, c: torch.nn.grad.conv2d_weight(c, w_shape, t, **g), gs, u, x, ux, what)
+        gw, ab, q = gw + p['sum'] / sc, ab + p['abs'] / sc, min(q, p['q'] / sc)
+        gb, abb, qb = gb + gs.double().sum((0, 2, 3)) / sc, abb + gs.double().abs().sum((0, 2, 3)) / sc, min(qb, u * X3_FINE / sc)
+        cross = {n_: cross[n_] + p[n_] / sc for n_ in cross}
+        nolo = nolo and float(p['lolo'].max()) == 0.0
+    return {'gw': x3_exact32(gw, what), 'gb': x3_exact32(gb, what + ' (bias)'), 'top': guard(what, ab, q), 'top_b': guard(what + ' (bias)', abb, qb),
+            'share': x3_cross_share(cross), 'nolo': nolo}
+
+
+def x3_slope01(pre64):
+    """The production slope 0.1 in the epilogue's own order (conv_x3.hip: `v *= winv; v = fmaxf(v, v * slope)`): the exact fp32
+    pre-activation, un-scaled, times float32(0.1) in fp32 where that is larger."""
+    return slope01_ref(pre64, torch.float32)
+
+
+# Forward layers.  Routes (upf_conv_x3_forward): 'tiled' = conv_x3_kernel<MTW = 1> in the halo width of the dilation (4: d <= 4, 8,
+# 16), stride 2 (halo 8) or 1x1; 'splitk' = conv_x3_sk_kernel (stride 1, >= 49 input channels, three products) in the same widths;
+# 'two' reaches MTW = 2 (Cout > 32 and tiles * ceil(ceil(Cout / 32) / 2) >= 256: 2 * 8 * 8 tiles of 8 x 32 pixels, two pairs of slabs).
+X3_FWD = [Layer('x5', 1, 5, 3, 3, 8), Layer('x17', 2, 17, 33, 7, 13), Layer('x16', 1, 16, 2, 9, 24), Layer('x243', 1, 243, 64, 3, 8),
+          Layer('x115', 1, 115, 32, 9, 24), Layer('x64one', 1, 64, 32, 1, 1), Layer('x17one', 1, 17, 32, 1, 1), Layer('x5tiny', 2, 5, 196, 2, 3),
+          Layer('x83d2', 1, 83, 3, 9, 24, d=2), Layer('x115d4', 1, 115, 32, 7, 13, d=4), Layer('x16d4', 1, 16, 33, 17, 56, d=4),
+          Layer('x64d8', 1, 64, 33, 17, 56, d=8), Layer('x64d8s', 1, 64, 3, 7, 13, d=8), Layer('x83d16', 1, 83, 32, 17, 56, d=16),
+          Layer('x64d16s', 1, 64, 2, 9, 24, d=16), Layer('x5d16s', 1, 5, 32, 3, 8, d=16),
+          Layer('x16s2', 2, 16, 32, 9, 24, s=2), Layer('x5s2', 1, 5, 33, 7, 13, s=2), Layer('x17s2', 1, 17, 64, 17, 56, s=2), Layer('x16s2t', 1, 16, 32, 2, 3, s=2),
+          Layer('x115p', 1, 115, 32, 7, 13, k=1), Layer('x243p', 2, 243, 3, 2, 3, k=1), Layer('x17p', 1, 17, 33, 9, 24, k=1), Layer('x64p', 1, 64, 128, 17, 56, k=1)]
+X3_TWO = Layer('x16two', 2, 16, 128, 64, 256)
+X3_FWD_BY_NAME = {l.name: l for l in X3_FWD + [X3_TWO]}
+X3_PLAIN = ('x17', 'x64d8', 'x16s2', 'x115p')          # run a second time with lo = 'disjoint': model == plain fp64 convolution
+X3_SLOPE01 = ('x17', 'x115', 'x16s2', 'x115p')         # the production slope: tiled (3 and 11 products), split-K, stride 2, 1x1
+X3_SCALE = ('x17', 'x115')                             # scale invariance: x * 2^-11, x * 2^14, w * 2^-20, w * 2^10
+X3_X_POW2 = (-11, 14)
+X3_W_POW2 = (-20, 10)
+X3_NONFINITE = ('x17', 'x115')
+X3_NF_VALUES = (float('inf'), float('nan'), 65520.0)
+
+
+def x3_splitk_eligible(layer):
+    return layer.s == 1 and (layer.Cin + 15) // 16 >= 4
+
+
+@functools.lru_cache(maxsize=None)
+def x3_forward_case(name, zeros=True, lo='all', x_pow2=0, w_pow2=0):
+    """-> (layer, operands, reference dict) of one forward layer, guarded; computed once and shared (nobody writes to them)."""
+    layer = X3_FWD_BY_NAME[name]
+    o = x3_operands(layer, zeros, lo, x_pow2, w_pow2)
+    return layer, o, x3_forward_ref(o, layer, 'x3 forward %s' % name)
+
+
+# Training layers: y, grad_x, grad_w, grad_b from one operand set.  (Cin, Cout and the pixel count are bounded by the quantum budget
+# of the gradients: with the slope 0.125 grad_pre's quantum is 8 times finer.)  The stride-2 layer is a 'disjoint' one: its data
+# gradient is the plain fp32 kernel.
+X3_TRAIN = [Layer('t17', 1, 17, 33, 7, 13), Layer('t5', 1, 5, 3, 3, 8), Layer('t16d2', 1, 16, 32, 5, 24, d=2), Layer('t33d4', 1, 33, 5, 9, 13, d=4),
+            Layer('t16s2', 2, 16, 33, 9, 24, s=2), Layer('t5s2', 1, 5, 32, 8, 14, s=2), Layer('t83p', 1, 83, 32, 7, 13, k=1), Layer('t64', 1, 64, 49, 7, 13)]
+X3_TRAIN_BY_NAME = {l.name: l for l in X3_TRAIN}
+X3_TRAIN_PLAIN = ('t17', 't83p')                       # also run with lo = 'disjoint'
+
+
+@functools.lru_cache(maxsize=None)
+def x3_train_case(name, slope=SLOPE, lo=None):
+    """-> (layer, operands, dict pre, y, ag, gx, gw, gb, tops, shares) of one training layer, every contraction guarded."""
+    layer = X3_TRAIN_BY_NAME[name]
+    lo = lo if lo is not None else ('disjoint' if layer.s == 2 else 'all')
+    o = x3_operands(layer, bool(slope), lo)
+    f = x3_forward_ref(o, layer, 'x3 train %s forward' % name)
+    ag = x3_act_grad_ref(o['gy'], f['pre'], slope)
+    dg = x3_dgrad_ref(ag, o, layer, 'x3 train %s data gradient' % name)
+    wg = x3_wgrad_ref([(o['x'], ag)], tuple(o['w'].shape), layer.d, layer.s, what='x3 train %s weight gradient' % name)
+    guard('x3 train %s bias runs' % name, ag['gs'].double().abs().sum((0, 2, 3)), ag['ug'] * X3_FINE)
+    ref = {'pre': f['pre'], 'y': x3_act(f['pre'], slope), 'ag': ag, 'gx': dg['gx'], 'gw': wg['gw'], 'gb': wg['gb'],
+           'tops': {'y': f['top'], 'gx': dg['top'], 'gw': wg['top'], 'gb': wg['top_b']}, 'shares': {'y': f['share'], 'gx': dg['share'], 'gw': wg['share']},
+           'plain': f['plain'], 'nolo': f['nolo'] and wg['nolo'] and dg.get('nolo', True)}
+    return layer, o, ref
+
+
+# act_grad_x3 alone: (B, C, H, W); B * H * W = 24, 91, 1, 255, 66: no multiple of the 32 runs, fewer elements than runs, one element
+X3_ACT_SHAPES = [(2, 5, 3, 4), (1, 33, 7, 13), (1, 3, 1, 1), (3, 2, 5, 17), (2, 64, 3, 11)]
+
+
+def x3_act_case(shape):
+    """-> gy, y (a fifth exact zeros, some negative), fp32 CPU."""
+    gen = torch.Generator().manual_seed(seed_of('x3act', shape))
+    gy = x3_values(shape, X3_XBASE, 1.0, gen)
+    y = x3_values(shape, X3_XBASE, 1.0, gen)
+    if gy.numel() > 4:
+        assert int((y == 0).sum()) >= 1 and int((y < 0).sum()) >= 1
+    return gy, y
+
+
+# data gradient alone: stride 1 on both routes (the forward kernel: K = the layer's OUTPUT channels), stride 2 with odd and even sizes
+X3_DGRAD = [Layer('g17', 2, 17, 33, 7, 13), Layer('g64', 1, 33, 64, 9, 24), Layer('g83d2', 1, 3, 83, 7, 13, d=2), Layer('g64p', 1, 32, 64, 3, 8, k=1),
+            Layer('g64d8', 1, 16, 64, 9, 24, d=8), Layer('g16s2', 2, 16, 32, 9, 24, s=2), Layer('g5s2', 1, 5, 33, 8, 14, s=2), Layer('g17s2', 1, 17, 3, 7, 13, s=2),
+            Layer('g3s2', 1, 3, 2, 2, 3, s=2)]
+X3_DGRAD_BY_NAME = {l.name: l for l in X3_DGRAD}
+X3_DGRAD_PLAIN_ONLY = ('g83d2',)                       # 83 x 9 terms: no room for the 8 times finer quantum of the slope 0.125
+
+
+@functools.lru_cache(maxsize=None)
+def x3_dgrad_case(name, slope=0.0):
+    layer = X3_DGRAD_BY_NAME[name]
+    o = x3_operands(layer, bool(slope), 'disjoint' if layer.s == 2 else 'all')
+    pre = x3_forward_ref(o, layer)['pre'] if slope else None
+    ag = x3_act_grad_ref(o['gy'], pre, slope)
+    return layer, o, ag, x3_dgrad_ref(ag, o, layer, 'x3 data gradient %s' % name)
+
+
+# weight gradient alone: conv (Cin, Cout, k, d, s) x levels [(B, H, W, power of two of grad_y)].  K chunks of 32 pixels, slices of
+# max(4, .) chunks: 216 pixels = 7 chunks = 2 slices; the small levels carry the large magnitudes (the budget counts in the finest
+# level's quantum).
+X3_WG_CONVS = {'w17': (17, 33, 3, 1, 1), 'w83p': (83, 32, 1, 1, 1), 'w16d4': (16, 2, 3, 4, 1), 'w5s2': (5, 3, 3, 1, 2), 'w40': (40, 70, 3, 1, 1),
+               'w115p': (115, 128, 1, 1, 1)}
+X3_WG_LEVELS = {1: [(2, 9, 12, 0)], 2: [(2, 7, 13, -1), (1, 3, 8, 1)],
+                6: [(1, 2, 3, 2), (2, 3, 8, 0), (1, 7, 13, -1), (1, 9, 24, -2), (3, 1, 1, 1), (1, 5, 9, 0)],
+                'act2': [(1, 7, 13, 0), (2, 3, 8, 1)]}
+X3_WG_CASES = [('w17', 1), ('w17', 2), ('w17', 6), ('w83p', 2), ('w83p', 6), ('w16d4', 6), ('w5s2', 1), ('w5s2', 6), ('w40', 2), ('w115p', 1)]
+X3_WG_ACT = ('w17', 'act2')                           # the levels go through the activation mask (slope 0.125, exact zeros in y)
+
+
+@functools.lru_cache(maxsize=None)
+def x3_wgrad_case(conv, n, scaled=True, lo='all', slope=0.0):
+    """-> (levels [(x, gy, y or None, act-grad dict)], reference dict).  lo = 'levels': the low halves of x and of grad_y sit in
+    different levels (one level: in different images or, B = 1, different rows) — the model is the plain fp64 gradient.
+    scaled = False: the NULL-slot uses (grad_pre split as it is)."""
+    Cin, Cout, k, d, s = X3_WG_CONVS[conv]
+    gen = torch.Generator().manual_seed(seed_of('x3wg', conv, n, lo))
+    uses, levels = [], []
+    for l, (B, H, W, m) in enumerate(X3_WG_LEVELS[n]):
+        ho, wo = out_hw(H, W, s)
+        lx = lg = None
+        if lo == 'levels' and len(X3_WG_LEVELS[n]) > 1:
+            lx, lg = torch.tensor(l % 2 == 0), torch.tensor(l % 2 == 1)
+        elif lo == 'levels':
+            lx = (torch.arange(B) % 2 == 0).view(-1, 1, 1, 1)
+            lg = ~lx
+        x = x3_values((B, Cin, H, W), X3_XBASE, 1.0, gen, lx)
+        gy = x3_values((B, Cout, ho, wo), X3_XBASE, 2.0 ** m, gen, lg)
+        y = x3_values((B, Cout, ho, wo), X3_XBASE, 1.0, gen) if slope else None
+        ag = x3_act_grad_ref(gy, y, slope, 2.0 ** m)
+        levels.append((x, gy, y, ag))
+        uses.append((x, ag if scaled else (ag['gpre'], 2.0 ** m * (slope if slope else 1.0))))
+        if not scaled:
+            _x3_halves(ag['gpre'], 2.0 ** m * (slope if slope else 1.0), 'NULL-slot grad_pre')
+    return levels, x3_wgrad_ref(uses, (Cout, Cin, k, k), d, s, what='x3 weight gradient %s/%s' % (conv, n))

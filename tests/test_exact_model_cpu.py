@@ -887,3 +887,158 @@ def test_msd_reference_fp32_error_is_nonzero_and_capped():
             assert all(em.on_grid(t, em.RESIZE_GRID[0]) and float(t.abs().max()) <= em.RESIZE_GRID[1] for t in levels + [y])
             assert max(errs) <= 1e-5 and max(chain) <= 1e-12                               # exact positions: a small bound
     assert set(em.MSD_REDRAWN) <= {c for c in em.msd_cases() if c[0] in em.MSD_ROUTE_CASES}
+
+
+# ---- the split-precision fp32 convolutions (tests/test_hip_conv_x3_exact.py) ----------------------------------------------------------
+# Guards (a) lossless split, (b) < 2^24 quanta of absolute terms and (c) a reference exact in fp32 are asserted INSIDE the *_case
+# functions of _exact_model (x3_products / guard / x3_exact32): building a case is running them.  Guard (d), the planted zeros and the
+# model-equals-truth cases are asserted here; the GPU file repeats (d) on the operands it runs.
+import math
+
+import _x3_model as xm
+
+
+def _log2(v):
+    return math.log2(v) if v > 0 else float('-inf')
+
+
+def test_x3_forward_cases_hold_their_guards():
+    top, share = 0.0, 1.0
+    for layer in em.X3_FWD + [em.X3_TWO]:
+        for zeros in (True, False):
+            _, o, ref = em.x3_forward_case(layer.name, zeros)
+            assert ref['top'] < em.LIMIT and ref['share'] > 0.5, (layer.name, ref['top'], ref['share'])
+            assert not ref['nolo'] and not ref['plain']                  # (the dropped lo * lo product is really there)
+            assert bool((ref['pre'] == 0).any()) == zeros, (layer.name, zeros)
+            # every non-zero operand half the kernel multiplies: x's low halves are non-zero on more than a third of the elements
+            lo = xm.split(o['x'])[1]
+            assert float((lo != 0).double().mean()) > 1.0 / 3 or layer.H * layer.W <= 6
+            top, share = max(top, ref['top']), min(share, ref['share'])
+    print('x3 forward: largest sum of |terms| = 2^%.2f quanta, smallest cross-product share %.2f' % (_log2(top), share))
+    # the cases of the route list really reach their routes' conditions (upf_conv_x3_forward)
+    assert {(l.k, min(l.d, 16) if l.s == 1 else 0) for l in em.X3_FWD if em.x3_splitk_eligible(l)} >= {(3, 1), (3, 2), (3, 4), (3, 8), (3, 16), (1, 1)}
+    assert {(l.k, l.d, l.s) for l in em.X3_FWD} >= {(3, 1, 1), (3, 2, 1), (3, 4, 1), (3, 8, 1), (3, 16, 1), (3, 1, 2), (1, 1, 1)}
+    for d in (8, 16):
+        hs = [l.H for l in em.X3_FWD if l.d == d]
+        assert min(hs) < d < max(hs)
+
+
+def test_x3_model_is_the_plain_fp64_convolution_where_no_pair_has_two_low_halves():
+    """x's low halves on even channels, w's on odd (ci, co): each cross product can be non-zero in at most half of the output
+    channels' terms, so guard (d) here asks for a quarter, not a half."""
+    for name in em.X3_PLAIN:
+        layer, o, ref = em.x3_forward_case(name, True, 'disjoint')
+        assert ref['nolo'] and ref['plain'] and ref['share'] > 0.25, (name, ref['share'])
+        assert bool((xm.split(o['x'])[1] != 0).any()) and bool((xm.split(em.x3_scaled_w(o['w'])[0])[1] != 0).any())
+    for name in em.X3_TRAIN_PLAIN:
+        layer, o, ref = em.x3_train_case(name, em.SLOPE, 'disjoint')
+        truth = em.layer_ref(o['x'], o['w'], o['b'], o['gy'], layer.k, layer.d, layer.s, em.SLOPE)
+        assert ref['plain'] and torch.equal(ref['y'], truth['y']) and torch.equal(ref['gx'], truth['gx']) and torch.equal(ref['gb'], truth['gb'])
+        assert torch.equal(ref['ag']['gpre'].double(), truth['gpre'])
+    for conv, n in em.X3_WG_CASES:
+        Cin, Cout, k, d, s = em.X3_WG_CONVS[conv]
+        levels, ref = em.x3_wgrad_case(conv, n, True, 'levels')
+        assert ref['nolo'] and ref['share'] > 0.5, (conv, n, ref['share'])
+        assert torch.equal(ref['gw'], em.wgrad_ref([(x, ag['gpre']) for x, _, _, ag in levels], (Cout, Cin, k, k), d, s))
+        assert torch.equal(ref['gb'], sum(ag['gpre'].double().sum((0, 2, 3)) for _, _, _, ag in levels))
+    # the stride-2 data gradient (a plain fp32 kernel): the model there is the plain fp64 gradient by construction
+    for layer in em.X3_DGRAD:
+        if layer.s == 2:
+            _, o, ag, ref = em.x3_dgrad_case(layer.name, em.SLOPE)
+            assert torch.equal(ref['gx'], torch.nn.grad.conv2d_input(o['x'].shape, o['w'].double(), ag['gpre'].double(), **em.geom(3, 1, 2)))
+
+
+def test_x3_torch_fp32_in_its_own_order_reproduces_the_reference():
+    """Order independence without a GPU: torch's fp32 convolution of the halves, three products summed in fp32, the scaled bias
+    added last (the kernels START at it), un-scaled — the reference's bits."""
+    for name in ('x17', 'x243', 'x64d8', 'x16s2', 'x115p'):
+        layer, o, ref = em.x3_forward_case(name, True)
+        ws, scw = em.x3_scaled_w(o['w'])
+        (xh, xl), (wh, wl) = xm.split(o['x']), xm.split(ws)
+        g = em.geom(layer.k, layer.d, layer.s)
+        acc = F.conv2d(xl.float(), wh.float(), None, **g) + F.conv2d(xh.float(), wl.float(), None, **g)
+        acc = acc + F.conv2d(xh.float(), wh.float(), None, **g) + (o['b'] * scw).view(1, -1, 1, 1)
+        assert torch.equal((acc / scw).double(), ref['pre']), name
+
+
+def test_x3_scale_cases_are_the_same_case_times_a_power_of_two():
+    for name in em.X3_SCALE:
+        _, o, ref = em.x3_forward_case(name, True)
+        for kx, kw in [(k, 0) for k in em.X3_X_POW2] + [(0, k) for k in em.X3_W_POW2]:
+            _, ok, refk = em.x3_forward_case(name, True, 'all', kx, kw)
+            assert torch.equal(ok['x'].double(), o['x'].double() * 2.0 ** kx) and torch.equal(ok['w'].double(), o['w'].double() * 2.0 ** kw)
+            assert torch.equal(ok['b'].double(), o['b'].double() * 2.0 ** (kx + kw))
+            assert torch.equal(refk['pre'], ref['pre'] * 2.0 ** (kx + kw)) and refk['top'] == ref['top']
+            assert em.x3_scaled_w(ok['w'])[1] == em.x3_scaled_w(o['w'])[1] * 2.0 ** -kw
+    lo = xm.split(em.x3_forward_case(em.X3_SCALE[0], True, 'all', -11, 0)[1]['x'])[1]
+    assert float(lo.abs().max()) == 2.0 ** -24                           # the last fp16 subnormal
+    assert float(em.x3_forward_case(em.X3_SCALE[0], True, 'all', 14, 0)[1]['x'].abs().max()) == 2.0 ** 15 + 2.0
+
+
+def test_x3_split_breaks_where_the_issue_says_it_does():
+    """A fine part of +-3 steps, or a fine part on a zero base, makes the fp16 high half fine-grained: guard (a)'s grid check refuses."""
+    base = torch.tensor([1.0, 2.0, -1.0])
+    em._x3_halves(base + em.X3_FINE, 1.0, 'one step')
+    with pytest.raises(AssertionError):
+        em._x3_halves(base + 5 * em.X3_FINE, 1.0, 'five steps')          # (past half an fp16 ulp of 1: hi is no longer the base)
+    with pytest.raises(AssertionError):
+        em._x3_halves(torch.tensor([em.X3_FINE]), 1.0, 'a step on a zero base')
+    with pytest.raises(AssertionError):
+        em._x3_halves(torch.randn(16), 2.0 ** -20, 'arbitrary fp32 values')
+
+
+def test_x3_training_and_gradient_cases_hold_their_guards():
+    tops, shares = {}, {}
+
+    def note(op, top, share=None):
+        tops[op] = max(tops.get(op, 0.0), top)
+        if share is not None:
+            shares[op] = min(shares.get(op, 1.0), share)
+
+    for layer in em.X3_TRAIN:
+        for slope in (em.SLOPE, 0.0):
+            _, o, ref = em.x3_train_case(layer.name, slope)
+            assert max(ref['tops'].values()) < em.LIMIT
+            zeros = ref['pre'] == 0
+            assert bool(zeros.any()) == bool(slope), layer.name
+            if slope:                                 # the zeros take the slope in the forward AND in the mask of the gradient
+                assert torch.equal(ref['ag']['gpre'].double()[zeros], o['gy'].double()[zeros] * slope) and bool((o['gy'][zeros] != 0).any())
+            for n in ('y', 'gx', 'gw'):
+                # stride 2: channel-disjoint low halves (each cross product in at most half of the terms) and a data gradient that
+                # forms no cross products at all (the plain fp32 kernel)
+                if layer.s == 1:
+                    assert ref['shares'][n] > 0.5, (layer.name, n, ref['shares'][n])
+                elif n != 'gx':
+                    assert ref['shares'][n] > 0.25, (layer.name, n, ref['shares'][n])
+                note('train ' + n, ref['tops'][n], ref['shares'][n] if layer.s == 1 else None)
+            note('train gb', ref['tops']['gb'])
+    for layer in em.X3_DGRAD:
+        for slope in (0.0, em.SLOPE):
+            if slope and layer.name in em.X3_DGRAD_PLAIN_ONLY:
+                continue
+            _, o, ag, ref = em.x3_dgrad_case(layer.name, slope)
+            assert ref['top'] < em.LIMIT
+            if layer.s == 1:
+                assert ref['share'] > 0.5, (layer.name, ref['share'])
+            note('dgrad s%d' % layer.s, ref['top'], ref['share'] if layer.s == 1 else None)
+    assert {l.H % 2 for l in em.X3_DGRAD if l.s == 2} == {0, 1} and {l.W % 2 for l in em.X3_DGRAD if l.s == 2} == {0, 1}
+    for conv, n in em.X3_WG_CASES + [em.X3_WG_ACT]:
+        slope = em.SLOPE if (conv, n) == em.X3_WG_ACT else 0.0
+        for scaled in (True, False):
+            levels, ref = em.x3_wgrad_case(conv, n, scaled, 'all', slope)
+            assert ref['top'] < em.LIMIT and ref['top_b'] < em.LIMIT and ref['share'] > 0.5, (conv, n, ref['share'])
+            note('wgrad', ref['top'], ref['share'])
+            note('wgrad bias', ref['top_b'])
+            if slope:
+                assert all(bool((y == 0).any()) and bool((y < 0).any()) for _, _, y, _ in levels)
+            assert len(levels) == 1 or len({ag['sc'] for _, _, _, ag in levels}) > 1          # the levels' scales differ
+    assert max(len(v) for v in em.X3_WG_LEVELS.values()) == 6            # MAXLV
+    for shape in em.X3_ACT_SHAPES:
+        gy, y = em.x3_act_case(shape)
+        for pre in (None, y):
+            ag = em.x3_act_grad_ref(gy, pre, em.SLOPE)
+            note('act_grad bias runs', em.guard('bias runs', ag['gs'].double().abs().sum((0, 2, 3)), ag['ug'] * em.X3_FINE))
+            assert ag['sc'] == xm.scale_of(ag['max']) and 2.0 ** 13 <= float(ag['gs'].abs().max()) < 2.0 ** 14
+            assert torch.equal(em.x3_bias_runs(ag['gs']).sum(1), ag['gs'].double().sum((0, 2, 3)))
+    for op in sorted(tops):
+        print('x3 %s: largest sum of |terms| = 2^%.2f quanta%s' % (op, _log2(tops[op]), ', smallest cross-product share %.2f' % shares[op] if op in shares else ''))

@@ -28,10 +28,10 @@ def _run(x, w, b, d, s, k, slope, nprod, off=5, launch=None):
     B, Cin, H, W = x.shape
     Cout = w.shape[0]
     ho, wo = ops.conv3x3_out_hw(H, W, s)
-    xbuf = torch.zeros(B, Cin + off, H, W, device='cuda')
-    xbuf[:, off:] = x
+    xbuf = torch.full((B, Cin + off + 1, H, W), float('nan'), device='cuda')       # NaN neighbours: a read outside the slice shows
+    xbuf[:, off:off + Cin] = x
     ybuf = torch.full((B, Cout + 3, ho, wo), 7.0, device='cuda')
-    xv = xbuf[:, off:]                                # a channel slice: 16-byte aligned rows for some (off, H, W), not for others
+    xv = xbuf[:, off:off + Cin]                                # a channel slice: 16-byte aligned rows for some (off, H, W), not for others
     assert ops.conv3x3_supported(xv, Cout, d, s, k)
     packed = ops.conv3x3_pack(w)
     prev = ops.CONV_X3_NPROD[0]
