@@ -865,6 +865,40 @@ int upf_png_encode_workspace_bytes(int B, int H, int W, int C, int depth, long l
 int upf_png_encode(const void* img, unsigned char* out, int* lengths, void* workspace, int B, int H, int W, int C, int depth,
                    void* stream);
 
+/* ---- KITTI error maps from the uint16 ground truth ---------------------------------------------------------------------------------
+ * The devkit's rendering of the end-point error against the ground truth, as the reference draws it (utils/tools.py:702-758,
+ * lib_to_show_flow.flow_error_image_np), as the payload of an 8-bit RGB PNG:
+ *   pred            fp32   [B,2,H,W] contiguous
+ *   gt_occ, gt_noc  uint16 [B,H,W,3] contiguous, as upf_kitti_score takes them
+ *   rgb             uint8  [B,H,W,3] R, G, B: what flow_io.write_png and upf_png_encode take as it is
+ * Per pixel, every step ONE fp32 operation rounded to nearest (no contraction), the divisions IEEE divisions (never a reciprocal
+ * multiply), sqrt the CORRECTLY ROUNDED fp32 square root:
+ *   gu, gv, m_occ = (float)(B_occ & 255), m_noc = (float)(B_noc & 255) exactly as upf_kitti_score; the flow is gt_occ's
+ *   diff = sqrt((pu-gu)*(pu-gu) + (pv-gv)*(pv-gv));   mag = sqrt(gu*gu + gv*gv)
+ * log_colors != 0:  err = min(diff / 3.0f, (20.0f * diff) / (mag + 1e-7f)), min as numpy's minimum (a NaN on either side gives NaN);
+ *   the colour is row i of the table, i the bin with lo[i] <= err < lo[i+1], lo = 0, 0.0625, 0.125, 0.25, 0.5, 1, 2, 4, 8, 16, 1e9:
+ *     (49,54,149) (69,117,180) (116,173,209) (171,217,233) (224,243,248) (254,224,144) (253,174,97) (244,109,67) (215,48,39) (165,0,38)
+ *   where m_noc == 1, else row i of the HALVED table — rint(255 * x) of what the reference returns, which stores float32(c/255)
+ *   and halves that; a constant table of its own, never a formula —
+ *     (25,27,75) (35,59,90) (58,87,105) (86,109,117) (112,122,124) (127,112,72) (127,87,49) (122,55,34) (108,24,20) (83,0,19)
+ *   no bin (err NaN, +-inf or >= 1e9): BLACK, as the reference.  m_occ == 0: (0,0,0).
+ * log_colors == 0:  e = min(diff, 5.0f) / 5.0f, b = rint((double)e * 255.0), a NaN gives 0;
+ *   R = b where m_occ != 0; G = B = b where m_occ != 0 and m_noc == 1; 0 everywhere else.
+ * Masks outside {0, 1}: a pixel is VALID when m_occ != 0 and NON-OCCLUDED when m_noc == 1.  The reference multiplies the image by
+ * mask_occ, so for masks outside {0, 1} this is a deviation; KITTI files hold only 0 and 1.
+ * dilate = r, 0 <= r <= 4 (not in the reference; KITTI ground truth is sparse and the plain map a dot pattern): a valid pixel keeps
+ * its colour; an invalid pixel takes the colour of the valid pixel that comes LAST in raster order (greatest y', then greatest x')
+ * within |y'-y| <= r, |x'-x| <= r inside the image; black when there is none.  r = 0 is the plain map.
+ * ONE launch on `stream` for every r: r = 0 renders 4 consecutive pixels per lane with the widest access the addresses allow (any
+ * H*W); r > 0 renders each 32 x 64 tile plus its halo once into LDS and resolves the windows there.  No workspace is needed:
+ * upf_flow_error_image_workspace_bytes answers 0 and `workspace` may be NULL (both are kept so that a later form may need one).
+ * No atomics, no workgroup waits for another; nothing but rgb is written; same bytes run to run.
+ * UPF_EINVAL: null pointers, non-positive sizes, dilate outside 0..4, a needed workspace missing; UPF_EUNSUPPORTED: 2^31 pixels or
+ * more; UPF_EALIGN: pred not 8-byte, gt_occ / gt_noc not 4-byte aligned (rgb: any address). */
+int upf_flow_error_image_workspace_bytes(int B, int H, int W, int dilate, long long* bytes);
+int upf_flow_error_image(const float* pred, const unsigned short* gt_occ, const unsigned short* gt_noc, unsigned char* rgb,
+                         int log_colors, int dilate, void* workspace, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

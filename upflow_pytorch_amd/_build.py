@@ -32,6 +32,7 @@ SOURCES = [
     ('ingest.hip', ['-ffp-contract=off']),          # (float64 subtract, divide, ONE rounding: the host data path's bits)
     ('score.hip', ['-ffp-contract=off']),           # (every fp32 step of the KITTI metrics rounds on its own: an exact F1 count)
     ('export.hip', ['-ffp-contract=off']),          # (the host writer's and the reference renderer's arithmetic, step by step)
+    ('errmap.hip', ['-ffp-contract=off']),          # (the reference's fp32 error and its bins, operation by operation)
     ('png.hip', []),                                # (integers only)
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function']

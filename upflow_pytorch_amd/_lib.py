@@ -120,6 +120,8 @@ SIGNATURES = {
     'upf_flow_export': [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp],
     'upf_png_encode_workspace_bytes': [_i, _i, _i, _i, _i, _c.POINTER(_ll), _c.POINTER(_ll)],
     'upf_png_encode': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    'upf_flow_error_image_workspace_bytes': [_i, _i, _i, _i, _c.POINTER(_ll)],
+    'upf_flow_error_image': [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp],
 }
 
 

@@ -10,6 +10,7 @@
 // correctly rounded as hipcc lowers it without fast-math, unlike the native 1-ulp instruction — so the outlier count is an exact
 // function of the inputs (tests/_score_model.py states it in numpy).
 #include "loss_common.hpp"
+#include "kitti_gt.hpp"
 
 namespace upf {
 namespace score {
@@ -27,15 +28,15 @@ static_assert(sizeof(Sums) == WORDS * 8, "one 8-byte word per sum");
 // one pixel: R, G, B of both ground-truth files (low 16 bits) and the prediction
 __device__ __forceinline__ void pixel(Sums& a, uint32_t ro, uint32_t go, uint32_t bo, uint32_t rn, uint32_t gn, uint32_t bn,
                                       float pu, float pv) {
-  const float gu = (float)((int)ro - 32768) * 0.015625f, gv = (float)((int)go - 32768) * 0.015625f;    // exact
-  const int io = (int)(bo & 255u), in = (int)(bn & 255u);                                              // np.uint8() wraps
+  const float gu = kitti::gt_flow(ro), gv = kitti::gt_flow(go);                                        // exact
+  const int io = kitti::gt_mask(bo), in = kitti::gt_mask(bn);                                          // np.uint8() wraps
   const float m_occ = (float)io, m_noc = (float)in;
   float du = gu - pu, dv = gv - pv;
   const float e_occ = sqrtf(du * du + dv * dv);
   const float thr = fmaxf(3.0f, sqrtf(gu * gu + gv * gv) * 0.05f);
   const float d_occ = e_occ * m_occ;
-  du = (float)((int)rn - 32768) * 0.015625f - pu;
-  dv = (float)((int)gn - 32768) * 0.015625f - pv;
+  du = kitti::gt_flow(rn) - pu;
+  dv = kitti::gt_flow(gn) - pv;
   const float e_noc = sqrtf(du * du + dv * dv);
   a.s_occ += (double)d_occ;
   a.n_occ += io;

@@ -303,22 +303,26 @@ class kitti_flow:
         def _device_scorer(self, test_model):
             """-> (score(batch, predflow), finish() -> the four averages) of the device_score path.  score enqueues, on the current
             stream behind the prediction: ops.kitti_score into row `index` of a device table, the copy of that row into a pinned
-            host table, an event.  Nothing in it reads a device value; the hook calls wait in `pending`."""
+            host table, an event.  Nothing in it reads a device value; the hook calls wait in `pending`.
+            A test model with a truthy attribute `wants_gt_u16` (Test_model(save=(..., 'error'))) also gets the two uint16 tensors, as
+            the keywords gt_occ_u16 / gt_noc_u16 of eval_save_result; `pending` keeps them alive until then.  Every other hook sees
+            the calls it always saw."""
             from collections import deque
             from .. import ops
             rows = max(len(self.dataset), 1)
             table = torch.zeros((rows, ops.SCORE_ROW), dtype=torch.float64, device='cuda')
             host = torch.zeros((rows, ops.SCORE_ROW), dtype=torch.float64).pin_memory()
-            pending = deque()                                             # (index, event, predflow, occmask), oldest first
+            pending = deque()                                             # (index, event, predflow, occmask, extra keywords), oldest first
+            wants_gt = bool(getattr(test_model, 'wants_gt_u16', False))
             count = [0]
 
             def deliver(keep):
                 # in order: everything whose row has arrived, and the oldest ones (waited for) while more than `keep` wait
                 while pending and (len(pending) > keep or pending[0][1].query()):
-                    index, ev, predflow, occmask = pending.popleft()
+                    index, ev, predflow, occmask, extra = pending.popleft()
                     ev.synchronize()
                     save_name = 'all_%.2f f1_%.1f noc_%.2f occ_%.2f__%d' % (tuple(host[index, :4].tolist()) + (index,))
-                    test_model.eval_save_result(save_name, predflow, occmask=occmask)
+                    test_model.eval_save_result(save_name, predflow, occmask=occmask, **extra)
 
             def score(batch, predflow):
                 index = count[0]
@@ -330,7 +334,7 @@ class kitti_flow:
                 occmask = (gt_occ[..., 2].to(torch.int32) & 255).to(torch.float32).unsqueeze(1)     # np.uint8() of the host path
                 ev = torch.cuda.Event()
                 ev.record()
-                pending.append((index, ev, predflow, occmask))
+                pending.append((index, ev, predflow, occmask, {'gt_occ_u16': gt_occ, 'gt_noc_u16': gt_noc} if wants_gt else {}))
                 deliver(self.save_lag)
 
             def finish():

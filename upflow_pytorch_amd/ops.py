@@ -2855,3 +2855,54 @@ def png_encode(img, out=None):
         raise UpflowHipError('%s: the lengths must be an int32 [%d] tensor, got %s %s' % (who, B, tuple(lengths.shape), lengths.dtype))
     _lib.launch(dev, 'upf_png_encode', _lib.ptr(img), _lib.ptr(streams), _lib.ptr(lengths), _lib.ptr(ws), B, H, W, C, depth)
     return streams, lengths
+
+
+# ---- KITTI error maps from the uint16 ground truth (csrc/errmap.hip) ---------------------------------------------------------------
+ERROR_DILATE_MAX = 4
+_errmap_ws = {}                                               # (device, stream, B, H, W, dilate) -> uint8 tensor, or None (no bytes needed)
+
+
+def flow_error_image_workspace(device, B, H, W, dilate):
+    """The cached workspace ops.flow_error_image uses for [B,2,H,W] predictions on `device`, per device, current stream and shape as
+    flow_export_workspace is — or None where upf_flow_error_image_workspace_bytes answers 0 bytes."""
+    import ctypes
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, B, H, W, dilate)
+    if key not in _errmap_ws:
+        nbytes = ctypes.c_longlong(0)
+        _lib.call('upf_flow_error_image_workspace_bytes', B, H, W, dilate, ctypes.byref(nbytes))
+        _errmap_ws[key] = torch.empty((nbytes.value,), dtype=torch.uint8, device=device) if nbytes.value > 0 else None
+    return _errmap_ws[key]
+
+
+def flow_error_image(pred, gt_occ_u16, gt_noc_u16, log_colors=True, dilate=0, out=None):
+    """The KITTI devkit's error map of every item (tools.lib_to_show_flow.flow_error_image_np; include/upflow_hip.h,
+    upf_flow_error_image) -> uint8 [B,H,W,3] on the device, R, G, B: the payload flow_io.write_png and ops.png_encode take as it
+    is.  pred fp32 [B,2,H,W]; gt_occ_u16 / gt_noc_u16: the payload of the two flow PNGs, uint16 [B,H,W,3], as ops.kitti_score takes
+    them.  log_colors: the devkit's ten-bin map (occluded pixels at half brightness), else min(error, 5) / 5 as brightness (red
+    where occluded); pixels without ground truth are black.  dilate = r in 0..4: every pixel without ground truth takes the colour of
+    the last valid pixel (in raster order) within r pixels — KITTI's ground truth is sparse.  out: a contiguous uint8 [B,H,W,3]
+    tensor to write (a slice of a larger one included).  One launch on the current stream, no host synchronisation."""
+    who = 'flow_error_image'
+    for name, t, dt in (('pred', pred, torch.float32), ('gt_occ_u16', gt_occ_u16, torch.uint16), ('gt_noc_u16', gt_noc_u16, torch.uint16)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 4:
+            raise UpflowHipError('%s: `%s` must be a 4-d %s tensor, got %s' % (who, name, dt, (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t)))
+    B, C, H, W = pred.shape
+    if C != 2 or min(B, H, W) < 1:
+        raise UpflowHipError('%s: pred [B,2,H,W] expected, got %s' % (who, tuple(pred.shape)))
+    for name, t in (('gt_occ_u16', gt_occ_u16), ('gt_noc_u16', gt_noc_u16)):
+        if tuple(t.shape) != (B, H, W, 3):
+            raise UpflowHipError('%s: `%s` must be [%d,%d,%d,3] (R, G, B of the KITTI flow PNG), got %s' % (who, name, B, H, W, tuple(t.shape)))
+    if isinstance(dilate, bool) or not isinstance(dilate, int) or not 0 <= dilate <= ERROR_DILATE_MAX:
+        raise UpflowHipError('%s: `dilate` must be an integer in 0..%d, got %r' % (who, ERROR_DILATE_MAX, dilate))
+    dev = _lib.check_gpu(pred, gt_occ_u16, gt_noc_u16, out)
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, 3):
+        raise UpflowHipError('%s: `out` must be a uint8 [%d,%d,%d,3] tensor, got %s %s' % (who, B, H, W, tuple(out.shape), out.dtype))
+    ws = flow_error_image_workspace(dev, B, H, W, dilate)
+    _lib.launch(dev, 'upf_flow_error_image', _lib.ptr(pred), _lib.ptr(gt_occ_u16), _lib.ptr(gt_noc_u16), _lib.ptr(out),
+                1 if log_colors else 0, dilate, _lib.ptr(ws), B, H, W)
+    return out

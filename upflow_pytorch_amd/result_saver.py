@@ -7,6 +7,7 @@ prediction to a ResultSaver, which
            <save_dir>/flow/<name>.png     the KITTI 16-bit flow PNG (a submission directory as it stands on the _test sets)
            <save_dir>/color/<name>.png    the Middlebury colour rendering
            <save_dir>/flo/<name>.flo
+           <save_dir>/error/<name>.png    the KITTI devkit's error map against the ground truth (ops.flow_error_image)
        and give the slot back.
 
 The caller never reads a device value.  A full ring blocks submit() until a worker is done with a slot; flush() waits for
@@ -15,7 +16,10 @@ everything outstanding and re-raises the first worker exception; close() does th
 png='device'  moves the compression of the two PNG kinds in front of the copy: step 1 goes on with ops.png_encode on the
 `kitti` / `color` payloads, step 2 copies the zlib streams' slots and their lengths instead of the samples, and a worker is left
 with the IDAT chunk's CRC and the write (flow_io.write_png_stream).  The files decode to the same samples; their bytes differ from
-the host writer's, which is why it is opt-in."""
+the host writer's, which is why it is opt-in.
+
+'error' is rendered from the uint16 ground truth — submit(..., gt_occ_u16=, gt_noc_u16=), which Evaluation_bench(device_score=True)
+supplies — by its own launch; when it is the only kind saved, ops.flow_export is not called."""
 import os
 import queue
 import threading
@@ -26,9 +30,11 @@ import torch
 from . import ops
 from .utils import flow_io
 
-# what can be saved -> (sub-directory, extension, key of ops.flow_export's result)
-KINDS = {'kitti': ('flow', '.png', 'kitti'), 'color': ('color', '.png', 'color'), 'flo': ('flo', '.flo', 'flo')}
-_WRITERS = {'kitti': flow_io.write_kitti_png_u16, 'color': flow_io.write_png, 'flo': lambda fn, a: flow_io.write_flo_payload(a, fn)}
+# what can be saved -> (sub-directory, extension, key of ops.flow_export's result; 'error' is ops.flow_error_image's)
+KINDS = {'kitti': ('flow', '.png', 'kitti'), 'color': ('color', '.png', 'color'), 'flo': ('flo', '.flo', 'flo'),
+         'error': ('error', '.png', 'error')}
+_WRITERS = {'kitti': flow_io.write_kitti_png_u16, 'color': flow_io.write_png, 'flo': lambda fn, a: flow_io.write_flo_payload(a, fn),
+            'error': flow_io.write_png}
 
 
 class _Slot(object):
@@ -46,13 +52,16 @@ class _Slot(object):
 
 
 class ResultSaver(object):
-    def __init__(self, save_dir, save=('kitti',), workers=4, max_rad=None, slots=None, png='host'):
+    def __init__(self, save_dir, save=('kitti',), workers=4, max_rad=None, slots=None, png='host', error_log_colors=True, error_dilate=0):
         save = (save,) if isinstance(save, str) else tuple(save)
         if not save or any(k not in KINDS for k in save):
             raise ValueError('ResultSaver: `save` must name some of %s, got %r' % (sorted(KINDS), save))
         if png not in ('host', 'device'):
             raise ValueError("ResultSaver: `png` must be 'host' or 'device', got %r" % (png,))
         self.png = png
+        if isinstance(error_dilate, bool) or not isinstance(error_dilate, int) or not 0 <= error_dilate <= ops.ERROR_DILATE_MAX:
+            raise ValueError('ResultSaver: `error_dilate` must be an integer in 0..%d, got %r' % (ops.ERROR_DILATE_MAX, error_dilate))
+        self.error_log_colors, self.error_dilate = bool(error_log_colors), error_dilate
         workers = int(workers)
         if workers < 1:
             raise ValueError('ResultSaver: at least one worker thread (got %d)' % workers)
@@ -71,11 +80,16 @@ class ResultSaver(object):
         sub, ext, _ = KINDS[kind]
         return os.path.join(self.save_dir, sub, name + ext)
 
-    def submit(self, save_name, predflow, occmask=None):
+    def submit(self, save_name, predflow, occmask=None, gt_occ_u16=None, gt_noc_u16=None):
         """predflow [B,2,H,W] (any float type) on the GPU, occmask [B,1,H,W] or None -> files named save_name (B = 1) or
-        save_name_<i>.  Returns as soon as the work is enqueued; blocks only while every slot of the ring is in flight."""
+        save_name_<i>.  gt_occ_u16 / gt_noc_u16: the payload of the two ground-truth flow PNGs, uint16 [B,H,W,3] on the GPU, read
+        by the 'error' kind only.  Returns as soon as the work is enqueued; blocks only while every slot of the ring is in flight."""
         if self.pool is None:
             raise RuntimeError('ResultSaver: closed')
+        if 'error' in self.save and (gt_occ_u16 is None or gt_noc_u16 is None):
+            raise ValueError("ResultSaver: saving 'error' needs the uint16 ground truth of the pair (gt_occ_u16, gt_noc_u16), which only "
+                             "Evaluation_bench(device_score=True) / kitti_2015_test(device_score=True) hands over; the plain path and "
+                             "the _test sets have none")
         pred = predflow.detach()
         pred = pred if pred.dtype == torch.float32 else pred.float()
         valid = None
@@ -83,7 +97,11 @@ class ResultSaver(object):
             valid = occmask.detach().to(device=pred.device, dtype=torch.float32).reshape(pred.shape[0], 1, pred.shape[2], pred.shape[3]).contiguous()
         slot = self.free.get()                                             # a full ring blocks the caller here
         try:
-            res = ops.flow_export(pred.contiguous(), valid, max_rad=self.max_rad, **{k: True for k in self.save})
+            pred = pred.contiguous()
+            exported = [k for k in self.save if k != 'error']
+            res = ops.flow_export(pred, valid, max_rad=self.max_rad, **{k: True for k in exported}) if exported else {}
+            if 'error' in self.save:
+                res['error'] = ops.flow_error_image(pred, gt_occ_u16, gt_noc_u16, log_colors=self.error_log_colors, dilate=self.error_dilate)
             host = {}
             for k in self.save:
                 payload = res[KINDS[k][2]]

@@ -23,7 +23,7 @@ PARAM_DICT = {
 
 class Test_model(tools.abs_test_model):
     def __init__(self, pretrain_path='./scripts/upflow_kitti2015.pth', dtype=torch.float32, graph=True, device='cuda', net=None, streams=1,
-                 save_dir=None, save=('kitti',), save_workers=4, max_rad=None, png='host'):
+                 save_dir=None, save=('kitti',), save_workers=4, max_rad=None, png='host', error_log_colors=True, error_dilate=0):
         """streams > 1: `Evaluation_bench` keeps that many frame pairs in flight (runtime.PipelinedEvaluation, through
         eval_forward_stream) instead of one at a time — same results, ~1.7x the pairs per second at KITTI's frame size.
         save_dir (not in the reference, whose runner saves on the host): eval_save_result writes, for every prediction, the files
@@ -31,13 +31,20 @@ class Test_model(tools.abs_test_model):
         Middlebury rendering, scaled by max_rad px or by each frame's own largest flow), 'flo' -> <save_dir>/flo/<name>.flo —
         encoded on the device (ops.flow_export) and compressed and written by at most save_workers threads (result_saver.py);
         flush() / close() wait for the files.  None: eval_save_result prints the name, as the reference's.
-        png='device': the PNGs are compressed on the device too (ops.png_encode; the same samples in other bytes)."""
+        png='device': the PNGs are compressed on the device too (ops.png_encode; the same samples in other bytes).
+        'error' in save -> <save_dir>/error/<name>.png, the KITTI devkit's error map against the ground truth (ops.flow_error_image;
+        error_log_colors: its log colour map, else brightness; error_dilate = r in 0..4 spreads the sparse ground truth's pixels over
+        r pixels).  It needs the uint16 ground truth, which Evaluation_bench(device_score=True) hands to a model whose
+        `wants_gt_u16` is set — as it is here; everywhere else eval_save_result raises a ValueError."""
         super(Test_model, self).__init__()
         self.saver = None
+        self.wants_gt_u16 = False
         if save_dir is not None:
             from .result_saver import ResultSaver
             self.save_dir = save_dir
-            self.saver = ResultSaver(save_dir, save=save, workers=save_workers, max_rad=max_rad, png=png)
+            self.saver = ResultSaver(save_dir, save=save, workers=save_workers, max_rad=max_rad, png=png,
+                                     error_log_colors=error_log_colors, error_dilate=error_dilate)
+            self.wants_gt_u16 = 'error' in self.saver.save
         supplied = net is not None
         if net is None:
             net_conf = UPFlow_net.config()
@@ -92,7 +99,7 @@ class Test_model(tools.abs_test_model):
             print(save_name)
             return
         occmask = kwargs.get('occmask', args[0] if args else None)
-        self.saver.submit(save_name, predflow, occmask)
+        self.saver.submit(save_name, predflow, occmask, gt_occ_u16=kwargs.get('gt_occ_u16'), gt_noc_u16=kwargs.get('gt_noc_u16'))
 
     def flush(self):
         """Wait until every file handed to eval_save_result is written; re-raises the first exception of a writer thread."""
@@ -106,15 +113,17 @@ class Test_model(tools.abs_test_model):
 
 
 def kitti_2015_test(pretrain_path='./scripts/upflow_kitti2015.pth', dtype=torch.float32, root=None, device_score=False,
-                    save_dir=None, save=('kitti',), save_workers=4, max_rad=None, png='host'):
+                    save_dir=None, save=('kitti',), save_workers=4, max_rad=None, png='host', error_log_colors=True, error_dilate=0):
     """device_score=True (not in the reference): undecoded items — uint8 frames, uint16 ground truth — and the metrics of every
     pair from one ops.kitti_score call on the device (Evaluation_bench(device_score=True)); the same four numbers.
-    save_dir, save, save_workers, max_rad, png: Test_model's; the files are complete when this returns."""
+    save_dir, save, save_workers, max_rad, png, error_log_colors, error_dilate: Test_model's; the files are complete when this
+    returns.  save=(..., 'error') needs device_score=True (the error map is rendered from the uint16 ground truth)."""
     from .dataset.kitti_dataset import kitti_flow
     # note that eval batch size should be 1 for KITTI 2012 and KITTI 2015 (image size may be different for different sequence)
     dataset = kitti_flow.kitti_train(name='2015_train', root=root, u8=True, gt_u16=True) if device_score else None
     bench = kitti_flow.Evaluation_bench(name='2015_train', if_gpu=True, batch_size=1, root=root, dataset=dataset, device_score=device_score)
-    testmodel = Test_model(pretrain_path=pretrain_path, dtype=dtype, save_dir=save_dir, save=save, save_workers=save_workers, max_rad=max_rad, png=png)
+    testmodel = Test_model(pretrain_path=pretrain_path, dtype=dtype, save_dir=save_dir, save=save, save_workers=save_workers, max_rad=max_rad, png=png,
+                           error_log_colors=error_log_colors, error_dilate=error_dilate)
     try:
         epe_all, f1, epe_noc, epe_occ = bench(testmodel)
     finally:

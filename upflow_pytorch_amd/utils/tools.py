@@ -6,7 +6,7 @@ namespace), so code written against the reference (`tools.torch_warp(x, flo)`,
 keeps working; the arithmetic runs in the HIP kernels of libupflow_hip.so.
 File formats (.flo, KITTI flow PNG) live in utils/flow_io.py, the KITTI readers and the evaluation bench in
 dataset/kitti_dataset.py.  Out of scope: data prefetcher, SP_transform, visualisations other than
-flow_to_image.
+flow_to_image and the error map (lib_to_show_flow.flow_error_image_np; its arrows, point_vec, are not built).
 """
 import torch
 import torch.nn as nn
@@ -216,6 +216,55 @@ class tools():
                 col = np.where(rad <= 1, 1 - rad * (1 - col), col * 0.75)
                 img[:, :, i] = np.where(black, 0, np.floor(255 * col)).astype(np.uint8)
         return img
+
+    class lib_to_show_flow():
+        """The part of the reference's tools.lib_to_show_flow that an evaluation run uses (utils/tools.py:702-758); the device form
+        is ops.flow_error_image.  point_vec (arrows drawn with cv2) is out of scope."""
+        # the KITTI devkit's log colour map: error in [lower, upper) -> R, G, B
+        ERROR_COLORS = ((0, 0.0625, 49, 54, 149), (0.0625, 0.125, 69, 117, 180), (0.125, 0.25, 116, 173, 209),
+                        (0.25, 0.5, 171, 217, 233), (0.5, 1, 224, 243, 248), (1, 2, 254, 224, 144), (2, 4, 253, 174, 97),
+                        (4, 8, 244, 109, 67), (8, 16, 215, 48, 39), (16, 1e9, 165, 0, 38))
+
+        @classmethod
+        def flow_error_image_np(cls, flow_pred, flow_gt, mask_occ, mask_noc=None, log_colors=True):
+            """The end-point error of flow_pred against flow_gt (both [H,W,2]) as a colour image, float [H,W,3] in 0..1 with the
+            channels in B, G, R order, as the reference returns it.  mask_occ [H,W,1]: 1 at every pixel with ground truth;
+            mask_noc [H,W,1]: 1 where that pixel is not occluded (None: everywhere).
+            log_colors: the devkit's map of min(error / 3, 20 * error / |gt|) — the outlier criterion, 1 at its threshold — in ten
+            bins; occluded pixels at half brightness, pixels without ground truth black, as is an error no bin holds (NaN, inf,
+            1e9 and above).  Else: min(error, 5) / 5 as brightness, red where occluded.  The table is kept as float32(c / 255),
+            as the reference keeps it, so that 255 * image rounds to the same bytes."""
+            import numpy as np
+            if mask_noc is None:
+                mask_noc = np.ones(mask_occ.shape)
+            with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+                diff = np.sqrt(np.sum((flow_pred - flow_gt) ** 2, axis=2, keepdims=True))
+                if not log_colors:
+                    level = (np.minimum(diff, 5) / 5) * mask_occ
+                    seen = level * mask_noc
+                    return np.concatenate([seen, seen, level], axis=2)                     # B, G, R
+                table = np.asarray(cls.ERROR_COLORS, dtype=np.float32)
+                table[:, 2:] = table[:, 2:] / 255
+                mag = np.sqrt(np.sum(np.square(flow_gt), axis=2, keepdims=True))
+                err = np.minimum(diff / 3, 20 * diff / (mag + 1e-7))
+                im = np.zeros(err.shape[:2] + (3,))
+                for row in table:
+                    inside = np.logical_and(err >= row[0], err < row[1])                   # [H,W,1]: broadcasts over the channels
+                    im = np.where(inside, row[2:].astype(np.float64), im)
+                im = np.where(mask_noc == 1, im, im * 0.5)
+                im = im * mask_occ
+            return im[:, :, ::-1]
+
+    @classmethod
+    def flow_error_image_u8(cls, flow_pred, flow_gt, mask_occ, mask_noc=None, log_colors=True):
+        """lib_to_show_flow.flow_error_image_np as the bytes of an 8-bit RGB image, uint8 [H,W,3] in R, G, B order:
+        rint(255 * image) in float64, a NaN as 0 — what ops.flow_error_image renders on the device, so that host and device write
+        the same file (flow_io.write_png takes it as it is)."""
+        import numpy as np
+        im = cls.lib_to_show_flow.flow_error_image_np(flow_pred, flow_gt, mask_occ, mask_noc, log_colors)
+        with np.errstate(invalid='ignore'):
+            x = np.rint(255.0 * im[:, :, ::-1].astype(np.float64))
+            return np.where(np.isnan(x), 0.0, x).astype(np.uint8)
 
     class abs_test_model():
         """Evaluation protocol of utils/tools.py:157-164."""
